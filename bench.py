@@ -13,7 +13,13 @@ canonical bytes per record), one globally key-sorted set cut into N equal-count 
 shards.  Strong scaling: at N = 1 one MI355X holds all 100 M records (the north_star target);
 at N = 8 each GPU holds 12.5 M.  `--config config2` is BASELINE configs[1] (10 M per GPU, weak).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config config1|config2|config3|config3_full|config4|config5|encoded|snapshot|rbsr|bench_u32]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR] [--config config1|config2|config3|config3_full|config4|config5|encoded|snapshot|rbsr|bench_u32]
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what takes runs
+of its own: the oracle spot-check before timing, the CPU baselines, the end-to-end leg, and the
+side measurements of `encoded` (the map path, the schema kernel's ratio) and `snapshot` (the fused
+pass's roofline).  --dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy;
+the inputs are seeded, so two builds run with the same arguments can be compared array for array.
 
 --gpus N > 1 without a launcher: bench.py starts `python -m torch.distributed.run
 --nproc-per-node N` as a child process (no exec) and exits with its status; under a launcher
@@ -91,6 +97,15 @@ def parse():
                         "per GPU for the others")
     p.add_argument("--ranges", type=int, default=16)
     p.add_argument("--dump-aggregates", default="", help="write the step's combined range aggregates (JSON) here")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write what the last of them returned as DIR/<name>.npy (the "
+                        "arrays' bytes as float32, counts as float64; a fixed seeded sample of rows where an "
+                        "array is large, under 64 MB in all)")
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline figure: the oracle spot-check, the CPU baselines, the end-to-end "
+                        "leg and each config's side measurements and cross-checks (--check, --cpu-baseline, "
+                        "--e2e and --cpu-sample only apply with it); without it a run sets up, warms up, times "
+                        "the steps and prints the line")
     p.add_argument("--cpu-baseline", type=int, default=1, help="0 to skip the CPU baseline leg")
     p.add_argument("--cpu-sample", type=int, default=0,
                    help="records in the CPU baseline sample (0: min(shard, 10M), ~3 s of serial fill)")
@@ -113,7 +128,45 @@ def parse():
     p.add_argument("--spinup-ms", type=float, default=300.0,
                    help="untimed lift launches for this long before the warmup steps: the GPU raises its "
                         "clocks over the first ~50 ms of load (DESIGN.md section 6)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:  # a plain run measures the headline figure only
+        args.check = args.cpu_baseline = args.e2e = 0
+    return args
+
+
+DUMP_ROWS_BYTES = 2 << 20  # per dumped array: 2 Mi byte values = 8 MB of float32
+
+
+def _dump_sample(t: torch.Tensor):
+    """A tensor's rows as their bytes in float32, (rows, bytes per row).  Past DUMP_ROWS_BYTES the
+    rows of 64 equal windows: the first, the last and 62 at starts drawn from a fixed seed, copied
+    to the host window by window (contiguous slices, no gather)."""
+    import numpy as np
+    t = t.detach().contiguous()
+    rows = t.shape[0]
+    b = t.view(torch.uint8).view(rows, -1) if rows else t.view(torch.uint8).view(0, 1)
+    cap = max(DUMP_ROWS_BYTES // b.shape[1], 64)
+    if rows <= cap:
+        return b.cpu().numpy().astype(np.float32)
+    w = cap // 64
+    starts = np.sort(np.random.default_rng(20240).integers(0, rows - w + 1, size=62))
+    starts = [0] + [int(s) for s in starts] + [rows - w]
+    return np.concatenate([b[s:s + w].cpu().numpy() for s in starts]).astype(np.float32)
+
+
+def dump_outputs(d: str, arrays: dict) -> None:
+    """--dump-outputs: DIR/<name>.npy for every array the last timed step returned.  Tensors go
+    out as their bytes (float32, exact; _dump_sample), plain counts as float64."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            out = _dump_sample(a)
+        else:
+            out = np.asarray(a, dtype=np.float64)
+        np.save(os.path.join(d, name + ".npy"), out)
 
 
 def gpu_spinup(ms: float, dev) -> dict:
@@ -263,7 +316,7 @@ def main():
         checked = spot_check(schema, cols, n)
 
     lift_ms = []
-    state = {"pending": [], "res": None, "k": 0}
+    state = {"pending": [], "res": None, "ss": None, "k": 0}
 
     # each step's gather is combined on a side stream that waits for it (work.wait() inside the
     # side stream's context), so neither the compute stream nor the host ever waits for RCCL and
@@ -292,7 +345,7 @@ def main():
         if timed:
             e1.record(stream)
             lift_ms.append((e0, e1))
-        ss = reduce_blocks(bs)
+        ss = state["ss"] = reduce_blocks(bs)
         range_aggregates(fps, bs, ss, lo, hi, out=out)
         if dist is None:
             state["res"] = out
@@ -347,6 +400,11 @@ def main():
     if args.dump_aggregates:
         with open(args.dump_aggregates, "w") as f:
             json.dump({"world": world, "total": total, "ranges": [[int(x) for x in row] for row in root]}, f)
+    if args.dump_outputs:  # rank 0's shard (its lifts and sums) and the combined range aggregates
+        arrays = {"fingerprints": fps, "block_sums": bs, "super_sums": state["ss"], "range_aggregates": res}
+        if dual:
+            arrays.update({"projection_fingerprints": dual_out[2], "projection_block_sums": dual_out[3]})
+        dump_outputs(args.dump_outputs, arrays)
 
     recs = total * args.steps
     gib_s = recs * rec_bytes / elapsed / 2**30
@@ -553,6 +611,10 @@ def incremental(args, world, rank, dev, dist):
         if dump is not None:
             with open(args.dump_aggregates, "w") as f:
                 json.dump(dump, f)
+        if args.dump_outputs:  # the timed batches' counts and the whole map's root after the last
+            dump_outputs(args.dump_outputs, {
+                "root": root_g if dist is not None else torch.tensor([_agg_row(root_g)], dtype=torch.int64),
+                "batch_counts": counts})
         recs = applied[0]
         line = {
             "metric": "incremental update: batched inserts into a GPU-resident map (M records/s)",
@@ -665,17 +727,14 @@ def encoded(args, world, rank, dev, dist):
     public-api/rsos.txt:61): here [u8; 16] keys and Entry<Timestamp, Vec<u8>> of 64 B, 120 B each.
     A batch whose records share one length is hashed by the compile-time fixed-length kernel
     (k_lift_fixed_ct<120>).  One step = one device-resident lift + block sums of the n encoded
-    records (what rh_estore_load runs after its upload).  Also timed, once: the host encode
+    records (what rh_estore_load runs after its upload).  Also timed, once, with --full: the host encode
     (numpy, vectorised, for this fixed shape -- the Rust binding runs encode_to_vec per record), the
     fill (rh_estore_load from host bytes: the bulk path of just_insert_bulk /
     src/replica/write.rs:107-121 through the encoded store) and one 1 M-record batch
     (rh_estore_apply of rank-addressed inserts, the map's staged-batch flush).  The ABI calls are the
     ones HipEncodedMap::load_bulk / flush make; the Python map's own per-key index (a SortedList of
     Python objects) is not what is timed."""
-    import ctypes as C
-    import numpy as np
-    from rsos_hip import RecordSchema, lift_fixed, lift_records, reduce_blocks
-    from rsos_hip import _abi as A
+    from rsos_hip import RecordSchema, lift_fixed, lift_records
     from rsos_hip.synth import make_records, to_host
     kname, vname, kind, n_default, desc = CONFIGS["encoded"]
     n = args.records or n_default
@@ -687,6 +746,26 @@ def encoded(args, world, rank, dev, dist):
     t0 = time.perf_counter()
     rows = _encode_host(h)
     encode_s = time.perf_counter() - t0
+    map_path = _encoded_map_path(schema, h, rows, n, m, L, rank, dev, encode_s) if args.full else None
+    # device-resident steps: the encoded records' lift over bytes already in HBM
+    flat = torch.from_numpy(rows).to(dev).view(-1)
+    if args.full:
+        ref, _ = lift_records(schema, cols)
+        got, _ = lift_fixed(flat, L)
+        if not torch.equal(got, ref):
+            raise SystemExit("bench: encoded-bytes lift differs from the schema kernel's")
+        del got, ref
+    return _encoded_steps(args, world, rank, dev, dist, schema, cols, flat, n, L, map_path)
+
+
+def _encoded_map_path(schema, h, rows, n, m, L, rank, dev, encode_s):
+    """--config encoded --full: the map's fill and one batch through the encoded store's ABI, timed
+    once each and checked by the root (see encoded())."""
+    import ctypes as C
+    import numpy as np
+    from rsos_hip import lift_records
+    from rsos_hip import _abi as A
+    from rsos_hip.synth import make_records, to_host
     offs = np.arange(n + 1, dtype=np.uint64) * np.uint64(L)
     es = C.c_void_p()
     A.check(A.lib().rh_estore_create(dev.index, C.byref(es)), "rh_estore_create")
@@ -724,13 +803,19 @@ def encoded(args, world, rank, dev, dist):
     if int(present.sum()) == 0 and ((r1 - r0) % (1 << 256) != bsum or root1.size != n + m):
         raise SystemExit("bench: the encoded store's root after the batch differs from root + Σ batch lifts")
     A.lib().rh_estore_destroy(es)
-    # device-resident steps: the encoded records' lift over bytes already in HBM
-    flat = torch.from_numpy(rows).to(dev).view(-1)
-    ref, _ = lift_records(schema, cols)
-    got, _ = lift_fixed(flat, L)
-    if not torch.equal(got, ref):
-        raise SystemExit("bench: encoded-bytes lift differs from the schema kernel's")
-    del got
+    return {"host_encode_s": round(encode_s, 4), "host_encode_ns_per_record": round(encode_s / n * 1e9, 1),
+            "encoder": "numpy, vectorised for this fixed shape",
+            "fill_s": round(fill_s, 4), "fill_m_rec_per_s": round(n / fill_s / 1e6, 1),
+            "fill": "rh_estore_load from pageable host bytes (H2D + lift + sums + root)",
+            "batch": m, "batch_encode_s": round(bencode_s, 4), "apply_s": round(apply_s, 4),
+            "apply_m_rec_per_s": round(m / apply_s / 1e6, 1),
+            "apply": "rh_estore_apply: rank-addressed inserts (H2D + lift + segment merge + sums + root)",
+            "root_check": "root after the batch == root before + Σ schema-kernel lifts of the batch"}
+
+
+def _encoded_steps(args, world, rank, dev, dist, schema, cols, flat, n, L, map_path):
+    """--config encoded: the warmup and timed steps over the device-resident bytes, and the line."""
+    from rsos_hip import lift_fixed, lift_records
     spin = gpu_spinup(args.spinup_ms, dev)
     for _ in range(args.warmup):
         lift_fixed(flat, L)
@@ -743,7 +828,7 @@ def encoded(args, world, rank, dev, dist):
     for _ in range(args.steps):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        _, bs = lift_fixed(flat, L)
+        fps, bs = lift_fixed(flat, L)
         e1.record()
         ev.append((e0, e1))
     torch.cuda.synchronize()
@@ -756,16 +841,19 @@ def encoded(args, world, rank, dev, dist):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     kern_s = sum(a.elapsed_time(c) for a, c in ev) / len(ev) / 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"fingerprints": fps, "block_sums": bs})
+    del fps
     # the schema kernel on the same records, for the ratio (median of 10)
     sev = []
-    for _ in range(10):
+    for _ in range(10 if args.full else 0):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         lift_records(schema, cols)
         e1.record()
         sev.append((e0, e1))
     torch.cuda.synchronize()
-    schema_s = sorted(a.elapsed_time(c) for a, c in sev)[5] / 1e3
+    schema_s = sorted(a.elapsed_time(c) for a, c in sev)[5] / 1e3 if sev else None
     if rank == 0:
         recs = n * args.steps * world
         hbm = (L + 32) * n / kern_s / 1e9
@@ -785,16 +873,11 @@ def encoded(args, world, rank, dev, dist):
             "roofline": {"bound": "hbm", "achieved": round(hbm, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(hbm / HBM_PEAK_GBS, 4), "traffic": None,
                          "kernel": "rh::k_lift_fixed_ct<120> (lift + block sums)", "kernel_avg_us": round(kern_s * 1e6, 2)},
-            "schema_kernel_us": round(schema_s * 1e6, 2), "encoded_over_schema": round(kern_s / schema_s, 4),
-            "map_path": {"host_encode_s": round(encode_s, 4), "host_encode_ns_per_record": round(encode_s / n * 1e9, 1),
-                         "encoder": "numpy, vectorised for this fixed shape",
-                         "fill_s": round(fill_s, 4), "fill_m_rec_per_s": round(n / fill_s / 1e6, 1),
-                         "fill": "rh_estore_load from pageable host bytes (H2D + lift + sums + root)",
-                         "batch": m, "batch_encode_s": round(bencode_s, 4), "apply_s": round(apply_s, 4),
-                         "apply_m_rec_per_s": round(m / apply_s / 1e6, 1),
-                         "apply": "rh_estore_apply: rank-addressed inserts (H2D + lift + segment merge + sums + root)",
-                         "root_check": "root after the batch == root before + Σ schema-kernel lifts of the batch"},
         }
+        if args.full:
+            line["schema_kernel_us"] = round(schema_s * 1e6, 2)
+            line["encoded_over_schema"] = round(kern_s / schema_s, 4)
+            line["map_path"] = map_path
         if args.cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(schema, cols, args.cpu_sample or min(n, 10_000_000))
         print(json.dumps(line), flush=True)
@@ -844,24 +927,29 @@ def reload(args, world, rank, dev, dist):
     ok = root.size == n == info.keys and root.fingerprint.limbs == tuple(int(x) & (2**64 - 1) for x in want[0, :4])
     if not ok:
         raise SystemExit("bench: reloaded root aggregate differs from the lifted source rows")
-    # roofline of the dominant kernel, the fused pass k_snap_lift (listing + both lifts + keys +
-    # samples + block sums), timed with HIP events on the loading store's stream
-    # (rh_debug_reload_timing): algorithmic bytes = the file read once + per entry two
+    if args.dump_outputs and rank == 0:  # what the last reload left: both stores' roots and its counts
+        dump_outputs(args.dump_outputs, {
+            "dated_root": torch.tensor([_agg_row(root)], dtype=torch.int64),
+            "projection_root": torch.tensor([_agg_row(proj.aggregate())], dtype=torch.int64),
+            "entries": [info.keys, info.tombstones]})
+    # --full: roofline of the dominant kernel, the fused pass k_snap_lift (listing + both lifts +
+    # keys + samples + block sums), timed with HIP events on the loading store's stream over three
+    # more reloads (rh_debug_reload_timing): algorithmic bytes = the file read once + per entry two
     # fingerprints, the key once per store and the two stores' search samples (1 u64 per 8 keys)
     import ctypes as C
     from rsos_hip import _abi as A
     lib = A.lib()
-    lib.rh_debug_reload_timing(1)
+    lib.rh_debug_reload_timing(1 if args.full else 0)
     stages = []
-    for _ in range(3):
+    for _ in range(3 if args.full else 0):
         load_snapshot(blob, dated, proj)
         loc, lift = C.c_double(), C.c_double()
         lib.rh_debug_last_reload_us(C.byref(loc), C.byref(lift))
         stages.append((lift.value, loc.value))
     lib.rh_debug_reload_timing(0)
-    lift_us, locate_us = min(stages)
+    lift_us, locate_us = min(stages) if stages else (0.0, 0.0)
     alg_bytes = file_bytes + n * (2 * 32 + 2 * sd.key_row + 2)
-    achieved = alg_bytes / (lift_us * 1e-6) / 1e9
+    achieved = alg_bytes / (lift_us * 1e-6) / 1e9 if stages else 0.0
     if rank == 0:
         recs = n * args.steps * world
         line = {
@@ -884,7 +972,9 @@ def reload(args, world, rank, dev, dist):
                          "locate_us": round(locate_us, 1)},
             "root_check": "dated root == Σ lift(source rows)",
         }
-        valu = load_valu("snapshot", n, lift_us * 1e-6)  # the fused pass is VALU-bound, like the lift
+        if not args.full:
+            del line["roofline"]
+        valu = load_valu("snapshot", n, lift_us * 1e-6) if args.full else None  # the fused pass is VALU-bound, like the lift
         if valu:
             line["valu"] = valu
         if args.e2e == 1:  # the file's bytes in (pinned) host memory: H2D inside the reload
@@ -971,6 +1061,8 @@ def reconcile(args, world, rank, dev, dist):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     if rank == 0:
+        if args.dump_outputs:  # the last reconciliation's rounds, segments answered and ranges enumerated
+            dump_outputs(args.dump_outputs, {"reconciliation": [rounds, segs, enum]})
         line = {
             "metric": "rbsr reconciliation on GPU stores (segments answered per second)",
             "value": round(segs * args.steps * world / elapsed / 1e6, 3), "unit": "M segments/s",

@@ -10,7 +10,7 @@
 #   pytest_k          the GPU tests matching $PYTEST_K
 #   smoke             __graft_entry__.smoke()
 #   default config5 config5_40 rbsr snapshot encoded config2 config3
-#                     one bench.py line each (the default is configs[3] at N = 1)
+#                     one bench.py --full line each (the default is configs[3] at N = 1)
 #   prof_config4      rocprofv3 kernel stats, FETCH_SIZE / WRITE_SIZE and VALU passes of the
 #                     default line at $RECORDS (100 M unless set), summarised into <tag>_*.json
 #   prof_cfg          the same four passes for $CFG at $RECORDS (kernel $KRE, default k_lift),
@@ -70,12 +70,12 @@ for step in "$@"; do
     pytest) run pytest 900 python -u -m pytest tests -m gpu -q -rf --maxfail=3 --timeout 300 --timeout-method thread ;;
     pytest_k) run pytest_k 700 python -u -m pytest tests -m gpu -k "${PYTEST_K:?}" -q -rf --maxfail=3 --timeout 300 --timeout-method thread ;;
     smoke) run smoke 200 python3 -c "import __graft_entry__ as g; g.smoke()" ;;
-    default) run default 300 python3 bench.py ;;
-    config5) run config5 300 python3 bench.py --config config5 ;;
-    config5_40) run config5_40 300 python3 bench.py --config config5 --steps 40 ;;
+    default) run default 300 python3 bench.py --full ;;
+    config5) run config5 300 python3 bench.py --full --config config5 ;;
+    config5_40) run config5_40 300 python3 bench.py --full --config config5 --steps 40 ;;
     config5_ab)  # the batch's result block by a kernel store (default) / a copy command, twice each
         for k in 1a 0a 1b 0b; do run config5_ab_$k 300 env RSOS_HIP_COPY_KERNEL=${k%?} python3 bench.py --config config5 --steps 40 --cpu-baseline 0; done ;;
-    rbsr) run rbsr 300 python3 bench.py --config rbsr ;;
+    rbsr) run rbsr 300 python3 bench.py --full --config rbsr ;;
     trace_rbsr)
         run trace_rbsr 300 rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d "$O/trrb" -o tr -- python3 bench.py --config rbsr --cpu-baseline 0 --steps 5 --warmup 2
         python3 scripts/write_timeline.py "$O/trrb" k_round_bounds > "$O/${TAG}_rbsr_round_timeline.txt" 2>&1 || true
@@ -87,10 +87,10 @@ for step in "$@"; do
         run rbsr_copyin0b 300 env RSOS_HIP_ROUND_COPYIN=0 python3 bench.py --config rbsr --cpu-baseline 0 &&
         run rbsr_copyin1b 300 env RSOS_HIP_ROUND_COPYIN=1 python3 bench.py --config rbsr --cpu-baseline 0 ;;
     rbsr_host) run rbsr_host 300 env RSOS_HIP_ROUND_DBG=2 python3 bench.py --config rbsr --cpu-baseline 0 ;;
-    snapshot) run snapshot 300 python3 bench.py --config snapshot ;;
-    encoded) run encoded 300 python3 bench.py --config encoded ;;
-    config2) run config2 300 python3 bench.py --config config2 ;;
-    config3) run config3 300 python3 bench.py --config config3 ;;
+    snapshot) run snapshot 300 python3 bench.py --full --config snapshot ;;
+    encoded) run encoded 300 python3 bench.py --full --config encoded ;;
+    config2) run config2 300 python3 bench.py --full --config config2 ;;
+    config3) run config3 300 python3 bench.py --full --config config3 ;;
     prof_config4)
         R=$RECORDS
         run stats_c4_$R 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/stats_c4_$R" -o run -- $PMC_B
@@ -135,7 +135,7 @@ for step in "$@"; do
                 run sstore_prio${pr}_g$g 200 env RSOS_HIP_FORE_PRIORITY=$pr SSTORE_ROUNDS=1 $EX/sstore_client $g 2000000 100 1 20 || exit 1
             done
         done ;;
-    config3_full) run config3_full 600 python3 bench.py --config config3_full ;;
+    config3_full) run config3_full 600 python3 bench.py --full --config config3_full ;;
     prof_config5)
         run stats_c5 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/stats_c5" -o run -- python3 bench.py --config config5 --cpu-baseline 0
         cp "$O/stats_c5/run_kernel_stats.csv" "$O/${TAG}_config5_kernel_stats.csv"

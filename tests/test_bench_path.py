@@ -144,6 +144,91 @@ def test_config5_routed_batches_equal_one_store(tmp_path, gpu, world):
     torch.cuda.synchronize()
 
 
+PLAIN = ["--gpus", "1", "--records", "300001", "--steps", "3", "--warmup", "1", "--spinup-ms", "0"]
+
+
+@pytest.fixture(scope="module")
+def plain_run(tmp_path_factory, gpu):
+    """One plain run (no --full) of the default config at 300,001 records with its outputs dumped."""
+    d = tmp_path_factory.mktemp("dump")
+    r = _bench(PLAIN + ["--dump-outputs", str(d / "a"), "--dump-aggregates", str(d / "agg.json")])
+    assert r.returncode == 0, r.stderr[-3000:]
+    return d, json.loads(r.stdout.strip().splitlines()[-1])
+
+
+@pytest.mark.gpu
+def test_plain_run_reports_the_step_time_and_skips_the_side_legs(plain_run, gpu):
+    """Without --full: the headline fields and ms_per_step over exactly --steps steps, and none of
+    the legs that take runs of their own (oracle spot-check, CPU baseline, end to end).  With
+    --full the spot-check is back (the CPU baseline and end-to-end legs are switched off here by
+    their own options, which only apply with --full)."""
+    _, line = plain_run
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    # value (GiB/s) and ms_per_step describe the same three steps
+    gib = 300_001 * 120 / (line["ms_per_step"] * 1e-3) / 2**30
+    assert abs(gib - line["value"]) <= 0.01 * line["value"] + 0.01
+    assert line["oracle_spot_check"] is None and "cpu_baseline" not in line and "end_to_end" not in line
+    r = _bench(PLAIN + ["--full", "--cpu-baseline", "0", "--e2e", "0"])
+    assert r.returncode == 0, r.stderr[-3000:]
+    full = json.loads(r.stdout.strip().splitlines()[-1])
+    assert full["oracle_spot_check"].startswith("bit-exact")
+    assert full["metric"] == line["metric"] and full["unit"] == line["unit"]
+
+
+@pytest.mark.gpu
+def test_dumped_outputs_repeat_and_are_the_steps_arrays(plain_run, gpu):
+    """--dump-outputs: float32 .npy files under 64 MB in all, identical from run to run, holding
+    the bytes the last step returned: the sampled fingerprint windows start with the set's first
+    rows and end with its last, and the range aggregates are the ones --dump-aggregates writes."""
+    import numpy as np
+    import torch
+    from rsos_hip import RecordSchema, lift_records
+    from rsos_hip.synth import make_records
+    d, _ = plain_run
+    r = _bench(PLAIN + ["--dump-outputs", str(d / "b")])
+    assert r.returncode == 0, r.stderr[-3000:]
+    names = sorted(os.listdir(d / "a"))
+    assert names == sorted(os.listdir(d / "b")) == ["block_sums.npy", "fingerprints.npy", "range_aggregates.npy",
+                                                     "super_sums.npy"]
+    a = {f[:-4]: np.load(d / "a" / f) for f in names}
+    for f in names:
+        assert a[f[:-4]].dtype == np.float32 and np.array_equal(a[f[:-4]], np.load(d / "b" / f)), f
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    n = 300_001
+    s = RecordSchema.dated("bytes16", "bytes64")
+    fps, bs = lift_records(s, make_records(s, n, seed=42, key_space=n))
+    got = a["fingerprints"]
+    w = got.shape[0] // 64  # 64 windows of w rows; the first and the last are the set's ends
+    assert got.shape[1] == 32 and 0 < got.shape[0] < n
+    assert np.array_equal(got[:w], fps[:w].cpu().numpy().astype(np.float32))
+    assert np.array_equal(got[-w:], fps[n - w:].cpu().numpy().astype(np.float32))
+    assert np.array_equal(a["block_sums"], bs.cpu().numpy().astype(np.float32))  # 1172 rows: whole
+    agg = np.array(json.loads((d / "agg.json").read_text())["ranges"], dtype=np.int64)
+    assert np.array_equal(a["range_aggregates"], agg.view(np.uint8).reshape(16, 40).astype(np.float32))
+    torch.cuda.synchronize()
+
+
+def test_dump_sample_is_fixed_and_keeps_both_ends():
+    """bench._dump_sample on the CPU: a small array goes out whole, a large one as 64 equal windows
+    whose rows are the same on every call and include the first and the last row."""
+    import numpy as np
+    import torch
+    import bench
+    small = torch.arange(40, dtype=torch.int64).view(8, 5)
+    assert np.array_equal(bench._dump_sample(small), small.numpy().view(np.uint8).reshape(8, 40).astype(np.float32))
+    rows = bench.DUMP_ROWS_BYTES // 4 * 3 + 1
+    big = torch.arange(rows, dtype=torch.int32)
+    got = bench._dump_sample(big)
+    assert got.dtype == np.float32 and got.shape == (bench.DUMP_ROWS_BYTES // 4 // 64 * 64, 4)
+    assert np.array_equal(got, bench._dump_sample(big))
+    val = (got.astype(np.uint8).view(np.int32)).ravel()
+    assert val[0] == 0 and val[-1] == rows - 1
+    w = got.shape[0] // 64
+    assert all(np.array_equal(np.diff(val[i * w:(i + 1) * w]), np.ones(w - 1, np.int32)) for i in range(64))
+
+
 def test_records_by_index_equal_the_rows_of_the_set():
     """bench.py's overwrites regenerate the picked resident rows from their global indices
     (make_records(indices=...)) instead of gathering them from the 10^8-row columns: the same bytes
