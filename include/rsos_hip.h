@@ -61,7 +61,17 @@ typedef enum rh_status {
  *   BYTES : [u8; L] / Vec<u8> / String of fixed byte length L
  *                           -> u64 LE length L, then the L bytes (:105-113,162-179)        */
 typedef enum rh_key_kind { RH_KEY_UNIT = 0, RH_KEY_U32 = 1, RH_KEY_U64 = 2, RH_KEY_BYTES = 3 } rh_key_kind;
-typedef enum rh_value_kind { RH_VAL_UNIT = 0, RH_VAL_U32 = 1, RH_VAL_U64 = 2, RH_VAL_BYTES = 3 } rh_value_kind;
+/* Value encodings: UNIT / U32 / U64 as the keys'; BYTES: a byte string of one length per map (value_len),
+ * u64 LE length then the bytes; VARBYTES: Vec<u8> / String / &str of a length that differs per
+ * record -- u64 LE length, then the bytes (:105-113) -- given as a heap and offsets (rh_var_values
+ * below).  schema.value_len must be 0 for VARBYTES (RH_ERR_ARG otherwise).                      */
+typedef enum rh_value_kind {
+    RH_VAL_UNIT = 0,
+    RH_VAL_U32 = 1,
+    RH_VAL_U64 = 2,
+    RH_VAL_BYTES = 3,
+    RH_VAL_VARBYTES = 4
+} rh_value_kind;
 
 /* What is hashed per record:
  *   PLAIN      : lift(k, v)                                   FingerprintTreeMap<K, V>
@@ -87,8 +97,34 @@ typedef struct rh_columns {
     const uint32_t *logical; /* DATED: Timestamp.hlc.logical  (LogicalCounter)           */
     const uint64_t *node;    /* DATED: Timestamp.node_id      (NodeId)                   */
     const uint8_t  *tags;    /* DATED/PROJECTION, nullable: 0 = State::Present, 1 = Tombstone */
-    const void     *values;  /* n * value_len bytes                                      */
+    const void     *values;  /* n * value_len bytes; VARBYTES: one rh_var_values (below)   */
 } rh_columns;
+
+/* The value column of a RH_VAL_VARBYTES schema: rh_columns.values points to one of these, always
+ * in HOST memory (the 16-byte alignment rule for device columns does not apply to that pointer).
+ * Value i = bytes[offsets[i] .. offsets[i + 1]): the values of a batch packed in one heap, in any
+ * order of placement, with or without gaps.  A row whose tag is 1 (Tombstone) or whose op is 1
+ * (delete) ignores its span, whatever its length.
+ * In host-column calls (rh_store_load / _apply / _stage) bytes and offsets are host pointers: no
+ * alignment or padding is asked of the heap (the library pads its own staging copy, which holds
+ * bytes[0 .. offsets[n])), and the offsets are validated -- offsets[0] <= ... <= offsets[n] <=
+ * bytes_len, else RH_ERR_ARG with the store unchanged.
+ * In _device / _async calls they are DEVICE pointers under rh_lift_encoded_async's contract: bytes
+ * 4-byte aligned, bytes_len a multiple of 4 and >= offsets[n], offsets 8-byte aligned.  Nothing is
+ * read before bytes or at or past bytes + bytes_len: device offsets that decrease or exceed
+ * bytes_len are a caller error that yields wrong fingerprints, never an out-of-range read.
+ * Accepted by rh_lift_records_async, rh_lift_dual_async (two passes), rh_store_create / _load /
+ * _load_device / _apply / _apply_device / _apply_device_many / _stage; every store question works
+ * as for any other value kind (values never take part in them).  Batches of this kind of any size
+ * take the large-batch route with separate lift and search launches: the fused lift + search
+ * kernel and the small-batch kernel are not built for it.  Not supported (RH_ERR_UNSUPPORTED,
+ * the message names VARBYTES): rh_sstore_create (refused before any device call),
+ * rh_store_load_snapshot, rh_snapshot_decode_device and rh_lift_host.                          */
+typedef struct rh_var_values {
+    const uint8_t  *bytes;     /* the value heap                                              */
+    const uint64_t *offsets;   /* n + 1 entries, non-decreasing                               */
+    uint64_t        bytes_len; /* readable size of `bytes`                                    */
+} rh_var_values;
 
 typedef struct rh_aggregate {
     uint64_t fingerprint[4]; /* Aggregate.fingerprint, LE limbs */
@@ -98,9 +134,12 @@ typedef struct rh_aggregate {
 /* ---- library ------------------------------------------------------------------------- */
 int         rh_abi_version(void);
 const char *rh_last_error(void);
-/* 1 if a specialised kernel exists for this schema, 0 if it needs the encoded path, <0 bad */
+/* 1 if a specialised kernel exists for this schema, 0 if it needs the encoded path, <0 bad.
+ * VARBYTES values: 1 with unit, u32, u64, 16- and 32-byte keys, 0 with any other key length.   */
 int         rh_schema_supported(const rh_schema *schema);
-/* canonical-encoding length of a present / tombstone record of this schema (host helper)   */
+/* canonical-encoding length of a present / tombstone record of this schema (host helper).
+ * VARBYTES values: the length of a present record with an EMPTY value -- the prefix the value's
+ * bytes follow (key, stamp, State variant, the value's u64 length); the tombstone length as ever. */
 int64_t     rh_schema_record_len(const rh_schema *schema, int tombstone);
 
 /* ---- device-resident batch API (all pointers are device pointers) -------------------- */
@@ -434,8 +473,10 @@ int rh_wire_decode_range_aggregates(const rh_schema *schema, int key_form, int m
                                     void *end_keys, rh_aggregate *aggregates, size_t *r_out, size_t *consumed);
 
 /* ---- the encoded store: Rsos<K> for any serde K / V -------------------------------------------
- * For keys and values without a fixed-width column form (ReplicatedMap<String, String>,
- * examples/k8s/main.rs:53; Vec<u8>, structs).  A record is its canonical bytes:
+ * For keys without a fixed-width column form (ReplicatedMap<String, String>,
+ * examples/k8s/main.rs:53; structs) and values that are neither a fixed-width column nor a byte
+ * string (a String / Vec<u8> value under a fixed-width key is RH_VAL_VARBYTES in the column
+ * store).  A record is its canonical bytes:
  * rsos::encoding::encode_to_vec(&k) followed by encode_to_vec(&v) (public-api/rsos.txt:61) --
  * lift(k, v) is BLAKE3 of exactly that concatenation (rsos/src/fingerprint.rs:270-275) -- hashed on
  * the device on ingest.  The caller keeps the keys and their order (the key type's Ord: for

@@ -6,6 +6,7 @@
 namespace rh {
 
 struct DevCols;
+struct VarCols;
 
 
 // Schema-specialised lift; returns hipErrorInvalidValue-free status, or sets *supported = false
@@ -14,6 +15,11 @@ hipError_t launch_lift_schema(int kk, int kl, int vk, int vl, int rk, bool tags,
                               const DevCols &c, uint64_t n, uint8_t *fps, uint8_t *bsums,
                               uint8_t *fps2, uint8_t *bsums2, hipStream_t st, bool *supported);
 bool schema_instantiated(int kk, int kl, int vk, int vl);
+// Variable-length values (lift_var.hpp; VarCols: c.values the heap, c.voffs, c.vlimit): unit, u32, u64,
+// 16- and 32-byte keys; *supported = false for any other key shape
+bool var_key_supported(int kk, int kl);
+hipError_t launch_lift_var(int kk, int kl, int rk, bool tags, const VarCols &c, uint64_t n, uint8_t *fps,
+                           uint8_t *bsums, hipStream_t st, bool *supported);
 
 hipError_t launch_lift_encoded(const uint8_t *bytes, const uint64_t *offs, uint64_t n, uint64_t limit,
                                uint8_t *fps, uint8_t *bsums, hipStream_t st);

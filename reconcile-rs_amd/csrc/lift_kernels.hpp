@@ -20,7 +20,7 @@
 namespace rh {
 
 enum { KEY_UNIT = 0, KEY_U32 = 1, KEY_U64 = 2, KEY_BYTES = 3 };
-enum { VAL_UNIT = 0, VAL_U32 = 1, VAL_U64 = 2, VAL_BYTES = 3 };
+enum { VAL_UNIT = 0, VAL_U32 = 1, VAL_U64 = 2, VAL_BYTES = 3, VAL_VARBYTES = 4 };
 enum { REC_PLAIN = 0, REC_DATED = 1, REC_PROJECTION = 2 };
 
 struct DevCols {
@@ -38,6 +38,14 @@ struct DevCols {
     // two-level positions: each input row's slot in its bucket's stretch, written in input order,
     // and each slot's sorted row, written in slot order -- both whole-line writes)
     const uint32_t *dst2 = nullptr;
+};
+
+// Columns with variable-length values (lift_var.hpp): `values` is the value heap, record i's
+// value is values[voffs[i] .. voffs[i + 1]), and nothing is read at or past values + vlimit.
+// (A type of its own: the schema kernels' argument block stays as it was.)
+struct VarCols : DevCols {
+    const uint64_t *voffs = nullptr;
+    uint64_t vlimit = 0;
 };
 
 constexpr int lowbit(int x) { return x & -x; }

@@ -22,6 +22,8 @@
 #include <atomic>
 #include <mutex>
 #include <string>
+#include <string_view>
+#include <unordered_set>
 #include <vector>
 
 #include "../../include/rsos_hip.h"
@@ -172,20 +174,25 @@ int value_row(const rh_schema &s) {
     case RH_VAL_UNIT: return 0;
     case RH_VAL_U32: return 4;
     case RH_VAL_U64: return 8;
+    case RH_VAL_VARBYTES: return 0;  // no fixed-width value column: a heap and offsets (rh_var_values)
     default: return (int)s.value_len;
     }
 }
+bool is_var(const rh_schema &s) { return s.value_kind == RH_VAL_VARBYTES; }
+const rh_var_values *var_of(const rh_columns &c) { return static_cast<const rh_var_values *>(c.values); }
 
 int check_schema(const rh_schema *s) {
     if (!s) return fail(RH_ERR_ARG, "schema is NULL");
     if (s->key_kind < 0 || s->key_kind > 3) return fail(RH_ERR_ARG, "bad key_kind");
-    if (s->value_kind < 0 || s->value_kind > 3) return fail(RH_ERR_ARG, "bad value_kind");
+    if (s->value_kind < 0 || s->value_kind > 4) return fail(RH_ERR_ARG, "bad value_kind");
     if (s->record_kind < 0 || s->record_kind > 2) return fail(RH_ERR_ARG, "bad record_kind");
     if (s->reserved != 0) return fail(RH_ERR_ARG, "schema.reserved must be 0");
     if (s->key_kind == RH_KEY_U32 && s->key_len != 4) return fail(RH_ERR_ARG, "u32 key needs key_len 4");
     if (s->key_kind == RH_KEY_U64 && s->key_len != 8) return fail(RH_ERR_ARG, "u64 key needs key_len 8");
     if (s->value_kind == RH_VAL_U32 && s->value_len != 4) return fail(RH_ERR_ARG, "u32 value needs value_len 4");
     if (s->value_kind == RH_VAL_U64 && s->value_len != 8) return fail(RH_ERR_ARG, "u64 value needs value_len 8");
+    if (s->value_kind == RH_VAL_VARBYTES && s->value_len != 0)
+        return fail(RH_ERR_ARG, "VARBYTES values need value_len 0 (lengths are per record)");
     return RH_OK;
 }
 
@@ -199,6 +206,18 @@ rh::DevCols to_dev(const rh_columns &c) {
     d.values = static_cast<const uint8_t *>(c.values);
     return d;
 }
+// VARBYTES: c.values is the host descriptor of a device heap
+rh::VarCols to_var_dev(const rh_schema &s, const rh_columns &c) {
+    rh::VarCols d;
+    static_cast<rh::DevCols &>(d) = to_dev(c);
+    if (is_var(s)) {
+        const rh_var_values *v = var_of(c);
+        d.values = v->bytes;
+        d.voffs = v->offsets;
+        d.vlimit = v->bytes_len;
+    }
+    return d;
+}
 
 int check_cols(const rh_schema &s, const rh_columns *c, size_t n) {
     if (!c) return fail(RH_ERR_ARG, "columns is NULL");
@@ -207,9 +226,35 @@ int check_cols(const rh_schema &s, const rh_columns *c, size_t n) {
     if (s.value_kind != RH_VAL_UNIT && !c->values) return fail(RH_ERR_ARG, "values column is NULL");
     if (s.record_kind == RH_REC_DATED && (!c->phys || !c->logical || !c->node))
         return fail(RH_ERR_ARG, "DATED records need phys / logical / node columns");
-    if (!aligned16(c->keys) || !aligned16(c->values) || !aligned16(c->phys) || !aligned16(c->node) ||
+    if (!aligned16(c->keys) || (!is_var(s) && !aligned16(c->values)) || !aligned16(c->phys) || !aligned16(c->node) ||
         !aligned16(c->logical))
         return fail(RH_ERR_ARG, "device columns must be 16-byte aligned");
+    if (is_var(s)) {  // the descriptor (host memory) of a device heap: rh_lift_encoded_async's contract
+        const rh_var_values *v = var_of(*c);
+        if (!v->offsets) return fail(RH_ERR_ARG, "VARBYTES: offsets is NULL");
+        if (v->bytes_len && !v->bytes) return fail(RH_ERR_ARG, "VARBYTES: bytes is NULL");
+        if (v->bytes_len % 4) return fail(RH_ERR_ARG, "VARBYTES: bytes_len must be a multiple of 4 (pad the heap)");
+        if (reinterpret_cast<uintptr_t>(v->bytes) % 4) return fail(RH_ERR_ARG, "VARBYTES: bytes must be 4-byte aligned");
+        if (reinterpret_cast<uintptr_t>(v->offsets) % 8) return fail(RH_ERR_ARG, "VARBYTES: offsets must be 8-byte aligned");
+    }
+    return RH_OK;
+}
+
+// Host columns of a VARBYTES schema: the descriptor and its offsets, checked before anything
+// changes (offsets[0] <= ... <= offsets[n] <= bytes_len).  A NULL descriptor stands for n empty
+// values (a delete-only batch), as a NULL value column does for the other kinds.
+int check_var_host(const rh_schema &s, const rh_columns &h, size_t n) {
+    if (!is_var(s) || n == 0 || !h.values) return RH_OK;
+    const rh_var_values *v = var_of(h);
+    if (!v->offsets) return fail(RH_ERR_ARG, "VARBYTES: offsets is NULL");
+    uint64_t prev = v->offsets[0];
+    for (size_t i = 1; i <= n; i++) {
+        const uint64_t o = v->offsets[i];
+        if (o < prev) return fail(RH_ERR_ARG, "VARBYTES: offsets decrease at row " + std::to_string(i - 1));
+        prev = o;
+    }
+    if (prev > v->bytes_len) return fail(RH_ERR_ARG, "VARBYTES: offsets[n] exceeds bytes_len");
+    if (prev && !v->bytes) return fail(RH_ERR_ARG, "VARBYTES: bytes is NULL");
     return RH_OK;
 }
 
@@ -219,6 +264,23 @@ int lift_dispatch(const rh_schema &s, const rh_columns &c, size_t n, uint8_t *fp
                   const uint32_t *dst2 = nullptr) {
     bool supported = false;
     if (dst_row && (bs || dual)) return fail(RH_ERR_STATE, "lift to sorted rows: no block sums (internal error)");
+    if (is_var(s)) {
+        rh::VarCols dc = to_var_dev(s, c);
+        dc.dst = dst_row;
+        dc.dst2 = dst2;
+        // two launches per lift (lift_var.hpp); the dual lift is two passes over the same columns
+        const bool tags = c.tags != nullptr && s.record_kind != RH_REC_PLAIN;
+        hipError_t ev = rh::launch_lift_var(s.key_kind, (int)s.key_len, s.record_kind, tags, dc, n, fps, bs, st,
+                                            &supported);
+        if (supported && ev == hipSuccess && dual)
+            ev = rh::launch_lift_var(s.key_kind, (int)s.key_len, RH_REC_PROJECTION, tags, dc, n, fps2, bs2, st,
+                                     &supported);
+        if (!supported)
+            return fail(RH_ERR_UNSUPPORTED, "VARBYTES values need a unit, u32, u64, 16- or 32-byte key; "
+                                            "canonical-encode on the host and use rh_lift_encoded_async");
+        if (ev != hipSuccess) return fail(RH_ERR_HIP, std::string("lift launch: ") + hipGetErrorString(ev));
+        return RH_OK;
+    }
     rh::DevCols dc = to_dev(c);
     dc.dst = dst_row;
     dc.dst2 = dst2;
@@ -386,6 +448,7 @@ int rh_schema_supported(const rh_schema *schema) {
     int rc = check_schema(schema);
     if (rc) return rc;
     const rh_schema &s = *schema;
+    if (is_var(s)) return rh::var_key_supported(s.key_kind, key_row(s)) ? 1 : 0;
     return rh::schema_instantiated(s.key_kind, (int)s.key_len, s.value_kind, (int)s.value_len) ? 1 : 0;
 }
 
@@ -397,7 +460,9 @@ int64_t rh_schema_record_len(const rh_schema *schema, int tombstone) {
     int64_t stamp = s.record_kind == RH_REC_DATED ? 20 : 0;
     if (s.record_kind == RH_REC_PLAIN) tombstone = 0;
     int64_t tag = s.record_kind == RH_REC_PLAIN ? 0 : 4;
-    int64_t val = tombstone ? 0 : (s.value_kind == RH_VAL_BYTES ? 8 + (int64_t)s.value_len : value_row(s));
+    // VARBYTES: the u64 length of an empty value (the prefix the value's bytes follow)
+    int64_t val = tombstone ? 0
+                            : (s.value_kind == RH_VAL_BYTES || is_var(s) ? 8 + (int64_t)s.value_len : value_row(s));
     return key + stamp + tag + val;
 }
 
@@ -510,19 +575,41 @@ struct DevColumns {
     DevBuf<uint64_t> phys, node;
     DevBuf<uint32_t> logical;
     bool has_tags = false;
+    // VARBYTES: `values` holds the heap copy (padded), voffs the n + 1 offsets; `var` is the
+    // descriptor view() hands out (it lives as long as this column set)
+    DevBuf<uint64_t> voffs;
+    rh_var_values var{nullptr, nullptr, 0};
 
+    // the heap bytes [0, offsets[n]) and the offsets as they are (checked by check_var_host); the
+    // copy is zero-padded to a multiple of 4, so no alignment or padding is asked of the caller
+    int upload_var(const rh_columns &h, size_t n, hipStream_t st) {
+        int rc;
+        const rh_var_values *v = var_of(h);
+        const uint64_t used = v && n ? v->offsets[n] : 0, padded = (used + 3) & ~uint64_t(3);
+        if ((rc = values.ensure(padded + 16)) || (rc = voffs.ensure(n + 1))) return rc;
+        if (used) RH_HIP(hipMemcpyAsync(values.p, v->bytes, used, hipMemcpyHostToDevice, st));
+        if (padded > used) RH_HIP(hipMemsetAsync(values.p + used, 0, padded - used, st));
+        if (v) RH_HIP(hipMemcpyAsync(voffs.p, v->offsets, (n + 1) * 8, hipMemcpyHostToDevice, st));
+        else RH_HIP(hipMemsetAsync(voffs.p, 0, (n + 1) * 8, st));  // no values given: n empty ones
+        var = rh_var_values{values.p, voffs.p, padded};
+        return RH_OK;
+    }
     int upload(const rh_schema &s, const rh_columns &h, size_t n, hipStream_t st) {
         int rc;
         const size_t kr = key_row(s), vr = value_row(s);
         if ((rc = keys.ensure(n * kr + 16))) return rc;
-        if ((rc = values.ensure(n * vr + 16))) return rc;
+        if (is_var(s)) {
+            if ((rc = upload_var(h, n, st))) return rc;
+        } else if ((rc = values.ensure(n * vr + 16))) {
+            return rc;
+        }
         // a NULL host column (e.g. the values of a delete-only batch) is zero-filled
         auto put = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
             if (!bytes) return hipSuccess;
             return src ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) : hipMemsetAsync(dst, 0, bytes, st);
         };
         RH_HIP(put(keys.p, h.keys, n * kr));
-        RH_HIP(put(values.p, h.values, n * vr));
+        if (!is_var(s)) RH_HIP(put(values.p, h.values, n * vr));
         if (s.record_kind == RH_REC_DATED) {
             if ((rc = phys.ensure(n)) || (rc = node.ensure(n)) || (rc = logical.ensure(n))) return rc;
             RH_HIP(put(phys.p, h.phys, n * 8));
@@ -539,7 +626,7 @@ struct DevColumns {
     rh_columns view(const rh_schema &s) const {
         rh_columns c;
         c.keys = keys.p;
-        c.values = values.p;
+        c.values = is_var(s) ? static_cast<const void *>(&var) : values.p;
         c.phys = s.record_kind == RH_REC_DATED ? phys.p : nullptr;
         c.node = s.record_kind == RH_REC_DATED ? node.p : nullptr;
         c.logical = s.record_kind == RH_REC_DATED ? logical.p : nullptr;
@@ -548,7 +635,7 @@ struct DevColumns {
     }
     void release() {
         keys.release(); values.release(); tags.release();
-        phys.release(); node.release(); logical.release();
+        phys.release(); node.release(); logical.release(); voffs.release();
     }
 };
 
@@ -608,6 +695,9 @@ extern "C" int rh_lift_host(int device, const rh_schema *schema, const rh_column
     int rc = check_schema(schema);
     if (rc) return rc;
     if (!h) return fail(RH_ERR_ARG, "columns is NULL");
+    if (is_var(*schema))
+        return fail(RH_ERR_UNSUPPORTED, "rh_lift_host does not take VARBYTES values: lift on the device "
+                                        "(rh_lift_records_async) or through a store");
     if (n == 0) return RH_OK;
     if (!host_fps) return fail(RH_ERR_ARG, "host_fps is NULL");
     RH_HIP(hipSetDevice(device));
@@ -806,9 +896,11 @@ struct rh_store {
         std::vector<uint8_t> keys, vals, tags, ops;
         std::vector<uint64_t> phys, node;
         std::vector<uint32_t> logical;
+        std::vector<uint64_t> vlen;  // VARBYTES: each row's value length (vals holds the ragged bytes)
         size_t n = 0;
         void clear() {
             keys.clear(), vals.clear(), tags.clear(), ops.clear(), phys.clear(), node.clear(), logical.clear();
+            vlen.clear();
             n = 0;
         }
     } pend;
@@ -820,7 +912,18 @@ struct rh_store {
             else v.resize(v.size() + cnt);
         };
         app(pend.keys, static_cast<const uint8_t *>(h.keys), m * kr);
-        app(pend.vals, static_cast<const uint8_t *>(h.values), m * vr);
+        if (is_var(schema)) {
+            // ragged: each row's bytes appended as they come (a delete keeps none)
+            const rh_var_values *v = var_of(h);
+            for (size_t i = 0; i < m; i++) {
+                const uint64_t a = v ? v->offsets[i] : 0, b = v ? v->offsets[i + 1] : 0;
+                const uint64_t len = ops[i] == 1 ? 0 : b - a;
+                if (len) pend.vals.insert(pend.vals.end(), v->bytes + a, v->bytes + a + len);
+                pend.vlen.push_back(len);
+            }
+        } else {
+            app(pend.vals, static_cast<const uint8_t *>(h.values), m * vr);
+        }
         app(pend.tags, h.tags, m);
         app(pend.ops, ops, m);
         if (dated) {
@@ -876,6 +979,16 @@ struct rh_store {
         if (!pend.n) return RH_OK;
         const size_t m = pend.n;
         const bool dated = schema.record_kind == RH_REC_DATED;
+        if (is_var(schema)) {
+            int rc;
+            try {
+                rc = flush_var();
+            } catch (const std::bad_alloc &) {
+                rc = fail(RH_ERR_OOM, "staged batch: host allocation failed");
+            }
+            pend.clear();
+            return rc;
+        }
         const rh_columns h{pend.keys.data(), dated ? pend.phys.data() : nullptr, dated ? pend.logical.data() : nullptr,
                            dated ? pend.node.data() : nullptr,
                            schema.record_kind == RH_REC_PLAIN ? nullptr : pend.tags.data(), pend.vals.data()};
@@ -883,6 +996,45 @@ struct rh_store {
         const int rc = apply_host(h, pend.ops.data(), m, c, true);
         pend.clear();
         return rc;
+    }
+    // The staged rows of a VARBYTES store: the last row of each key is chosen here, on the host,
+    // and the kept rows go up as one batch without repeats -- their values packed in staging order,
+    // so the device never gathers value bytes (the lift writes to the sorted rows after the sort).
+    int flush_var() {
+        const size_t m = pend.n, kr = kl;
+        const bool dated = schema.record_kind == RH_REC_DATED, plain = schema.record_kind == RH_REC_PLAIN;
+        std::vector<uint64_t> offs(m + 1, 0);
+        for (size_t i = 0; i < m; i++) offs[i + 1] = offs[i] + pend.vlen[i];
+        std::vector<uint8_t> last(m, 0);
+        size_t kept = 0;
+        {
+            std::unordered_set<std::string_view> seen;
+            seen.reserve(m * 2);
+            for (size_t i = m; i-- > 0;)
+                if (seen.emplace(reinterpret_cast<const char *>(pend.keys.data()) + i * kr, kr).second) last[i] = 1, kept++;
+        }
+        uint64_t c[3];
+        if (kept == m) {
+            const rh_var_values v{pend.vals.data(), offs.data(), offs[m]};
+            const rh_columns h{pend.keys.data(), dated ? pend.phys.data() : nullptr, dated ? pend.logical.data() : nullptr,
+                               dated ? pend.node.data() : nullptr, plain ? nullptr : pend.tags.data(), &v};
+            return apply_host(h, pend.ops.data(), m, c);
+        }
+        Pending q;
+        std::vector<uint64_t> qoffs{0};
+        for (size_t i = 0; i < m; i++) {
+            if (!last[i]) continue;
+            q.keys.insert(q.keys.end(), pend.keys.begin() + i * kr, pend.keys.begin() + (i + 1) * kr);
+            q.vals.insert(q.vals.end(), pend.vals.begin() + offs[i], pend.vals.begin() + offs[i + 1]);
+            qoffs.push_back(q.vals.size());
+            q.tags.push_back(pend.tags[i]);
+            q.ops.push_back(pend.ops[i]);
+            if (dated) q.phys.push_back(pend.phys[i]), q.node.push_back(pend.node[i]), q.logical.push_back(pend.logical[i]);
+        }
+        const rh_var_values v{q.vals.data(), qoffs.data(), qoffs[kept]};
+        const rh_columns h{q.keys.data(), dated ? q.phys.data() : nullptr, dated ? q.logical.data() : nullptr,
+                           dated ? q.node.data() : nullptr, plain ? nullptr : q.tags.data(), &v};
+        return apply_host(h, q.ops.data(), kept, c);
     }
     // host columns: a small batch is packed into page-locked memory the device reads in place;
     // a large one is uploaded (one copy per column) and applied by the large-batch path
@@ -905,6 +1057,7 @@ struct rh_store {
     uint64_t small_env = getenv("RSOS_HIP_SMALL_MAX") ? strtoull(getenv("RSOS_HIP_SMALL_MAX"), nullptr, 10) : ~0ull;
     uint64_t small_limit() const {
         if (schema.key_kind == RH_KEY_UNIT) return 0;
+        if (is_var(schema)) return 0;  // k_small_batch is not built for ragged values: the large-batch route
         return std::min<uint64_t>(small_env, rh::small_batch_max((int)kl));
     }
     PinnedVec<uint8_t> sb_in;    // a small host batch, packed (the device reads it in place)
@@ -2308,7 +2461,7 @@ struct rh_store {
         if (pre_minmax) *pre_minmax = false;
         const uint32_t *pos = scratch.u32(7, m);
         if (scratch.err) return fail(RH_ERR_OOM, "scratch allocation failed");
-        if (fused_lift_search) {
+        if (fused_lift_search && !is_var(schema)) {  // (k_lift_search is not built for ragged values)
             rh::DevCols dc = to_dev(c);
             dc.dst = pos;
             dc.dst2 = sort_s2o;
@@ -2524,6 +2677,8 @@ struct rh_store {
     DevBuf<uint8_t> lastops;
     int apply_last_rows(const rh_columns &c, const uint8_t *ops, size_t m, uint64_t out[3]) {
         int rc;
+        // (a VARBYTES store's staged repeats are resolved on the host, flush_var: no row gather here)
+        if (is_var(schema)) return fail(RH_ERR_STATE, "last-wins batch of VARBYTES rows (internal error)");
         const uint32_t *pos = scratch.u32(7, m);
         uint32_t *keep = scratch.u32(11, m + 1), *dst = scratch.u32(12, m + 1);
         if (scratch.err) return fail(RH_ERR_OOM, "scratch allocation failed");
@@ -3420,9 +3575,10 @@ int rh_store_load(rh_store *s, const rh_columns *h, size_t n) {
     // the row cap first: it is a property of the arguments (include/rsos_hip.h, "Row cap")
     if (n >= (1ull << 31)) return fail(RH_ERR_ARG, "store size limit (2^31 rows) exceeded: use rh_sstore_* for a larger map");
     if (!s || !h) return fail(RH_ERR_ARG, "NULL");
+    int rc;
+    if ((rc = check_var_host(s->schema, *h, n))) return rc;
     RH_LOCK_NOFLUSH(s);
     s->pend.clear();  // a load replaces the contents: staged rows before it are superseded
-    int rc;
     if ((rc = s->staging.upload(s->schema, *h, n, s->stream))) return rc;
     return s->load_device(s->staging.view(s->schema), n);
 }
@@ -3795,6 +3951,7 @@ int rh_store_stage(rh_store *s, const rh_columns *h, const uint8_t *ops, size_t 
     if (sc.key_kind != RH_KEY_UNIT && !h->keys) return fail(RH_ERR_ARG, "keys column is NULL");
     for (size_t i = 0; i < m; i++)
         if (ops[i] > 1) return fail(RH_ERR_ARG, "op must be 0 (insert) or 1 (delete)");
+    if (int rc = check_var_host(sc, *h, m)) return rc;
     std::lock_guard<std::mutex> g(s->mu);
     if (s->pend.n + m >= (1ull << 31)) return fail(RH_ERR_ARG, "pending batch limit (2^31 rows) exceeded");
     try {
@@ -3846,8 +4003,9 @@ int rh_store_set_compaction(rh_store *s, uint64_t divisor, uint64_t min_rows) {
 int rh_store_apply(rh_store *s, const rh_columns *h, const uint8_t *ops, size_t m, uint64_t *n_new,
                    uint64_t *n_over, uint64_t *n_del) {
     if (!s || !h || (m && !ops)) return fail(RH_ERR_ARG, "NULL");
-    RH_LOCK(s);
     int rc;
+    if ((rc = check_var_host(s->schema, *h, m))) return rc;
+    RH_LOCK(s);
     uint64_t c[3];
     if ((rc = s->apply_host(*h, ops, m, c))) return rc;
     if (n_new) *n_new = c[0];
@@ -4115,6 +4273,8 @@ int rh_snapshot_decode_device(const rh_schema *schema, int key_form, const void 
                               const rh_columns *o, size_t cap, rh_snapshot_info *info, void *stream) {
     int rc = check_schema(schema);
     if (rc) return rc;
+    if (is_var(*schema))
+        return fail(RH_ERR_UNSUPPORTED, "snapshot decode does not take VARBYTES values (fixed-width value columns only)");
     if ((!dev_bytes && len) || !o) return fail(RH_ERR_ARG, "NULL");
     if (!aligned16(dev_bytes)) return fail(RH_ERR_ARG, "snapshot bytes must be 16-byte aligned");
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -4152,6 +4312,8 @@ int rh_store_load_snapshot(rh_store *dated, rh_store *proj, int key_form, const 
                            int on_device, rh_snapshot_info *info, void *after_stream) {
     if (!dated && !proj) return fail(RH_ERR_ARG, "no store given");
     if (!bytes && len) return fail(RH_ERR_ARG, "bytes is NULL");
+    if (is_var((dated ? dated : proj)->schema) || (proj && is_var(proj->schema)))
+        return fail(RH_ERR_UNSUPPORTED, "snapshot reload does not take VARBYTES values (fixed-width value columns only)");
     if (dated && dated->schema.record_kind != RH_REC_DATED) return fail(RH_ERR_ARG, "dated store must be DATED");
     if (proj && proj->schema.record_kind != RH_REC_PROJECTION)
         return fail(RH_ERR_ARG, "projection store must be PROJECTION");

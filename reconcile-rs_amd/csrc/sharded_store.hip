@@ -1079,6 +1079,9 @@ extern "C" {
 
 int rh_sstore_create(const int *devices, int n, const rh_schema *schema, rh_sstore **out) {
     if (!devices || n < 1 || n > 64 || !schema || !out) return fail(RH_ERR_ARG, "sstore: bad arguments");
+    // before any device call: a sharded load cuts fixed-width value rows per shard
+    if (schema->value_kind == RH_VAL_VARBYTES)
+        return fail(RH_ERR_UNSUPPORTED, "sstore: VARBYTES values are not supported by the sharded store (use one rh_store)");
     rh_sstore *s = new (std::nothrow) rh_sstore();
     if (!s) return fail(RH_ERR_OOM, "sstore: host allocation failed");
     s->schema = *schema;

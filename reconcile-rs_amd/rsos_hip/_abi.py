@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(HERE, "_lib", "librsos_hip.so")
 OK, ERR_ARG, ERR_HIP, ERR_OOM, ERR_UNSUPPORTED, ERR_STATE, ERR_DATA = 0, -1, -2, -3, -4, -5, -6
 # schema enums (rsos_hip.h)
 KEY_UNIT, KEY_U32, KEY_U64, KEY_BYTES = 0, 1, 2, 3
-VAL_UNIT, VAL_U32, VAL_U64, VAL_BYTES = 0, 1, 2, 3
+VAL_UNIT, VAL_U32, VAL_U64, VAL_BYTES, VAL_VARBYTES = 0, 1, 2, 3, 4
 REC_PLAIN, REC_DATED, REC_PROJECTION = 0, 1, 2
 BLOCK, SUPER = 256, 65536
 FORM_ARRAY, FORM_VEC = 0, 1  # rh_key_form: [u8; L] | Vec<u8> / String
@@ -29,6 +29,10 @@ class Schema(C.Structure):
 class Columns(C.Structure):
     _fields_ = [("keys", C.c_void_p), ("phys", C.c_void_p), ("logical", C.c_void_p),
                 ("node", C.c_void_p), ("tags", C.c_void_p), ("values", C.c_void_p)]
+
+
+class VarValues(C.Structure):  # rh_var_values: what Columns.values points to for VAL_VARBYTES
+    _fields_ = [("bytes", C.c_void_p), ("offsets", C.c_void_p), ("bytes_len", C.c_uint64)]
 
 
 class Aggregate(C.Structure):

@@ -15,6 +15,8 @@ from . import _abi as A
 from .schema import RecordSchema
 
 COLS = ("keys", "phys", "logical", "node", "tags", "values")
+# a 'var' schema's values: `values` is the uint8 heap, `value_offsets` n + 1 int64 / uint64 offsets
+VAR_OFFSETS = "value_offsets"
 
 
 def _stream() -> int:
@@ -37,7 +39,7 @@ _NEED: Dict[tuple, tuple] = {}  # per schema: (column, row width) of every requi
 
 
 def _need(schema: RecordSchema) -> tuple:
-    key = (schema.key_row, schema.value_row, bool(schema.dated_kind))
+    key = (schema.key_row, schema.value_row, bool(schema.dated_kind), schema.is_var)
     got = _NEED.get(key)
     if got is None:
         need = [("keys", schema.key_row), ("values", schema.value_row)]
@@ -51,9 +53,21 @@ def _check_cols(schema: RecordSchema, cols: Dict[str, torch.Tensor]) -> int:
     """The row count, after checking every column the schema needs: present, a contiguous device
     tensor, and exactly n rows of its width (the kernels index rows by n)."""
     for k in cols:
-        if k not in COLS:
+        if k not in COLS and not (k == VAR_OFFSETS and schema.is_var):
             raise ValueError(f"unknown column {k!r}")
-    if schema.key_row:
+    if schema.is_var:
+        heap, offs = cols.get("values"), cols.get(VAR_OFFSETS)
+        if heap is None or offs is None:
+            raise ValueError(f"columns 'values' (the heap) and {VAR_OFFSETS!r} are required by {schema}")
+        if not (heap.is_cuda and heap.is_contiguous() and heap.dtype == torch.uint8 and heap.dim() == 1):
+            raise ValueError("the value heap must be a contiguous 1-D uint8 device tensor")
+        if not (offs.is_cuda and offs.is_contiguous() and offs.element_size() == 8 and offs.dim() == 1
+                and offs.numel() >= 1):
+            raise ValueError(f"{VAR_OFFSETS!r} must be a contiguous 1-D int64 / uint64 device tensor of n + 1 entries")
+        n = offs.numel() - 1
+        if schema.key_row and cols.get("keys") is not None and cols["keys"].nbytes != n * schema.key_row:
+            raise ValueError(f"column 'keys' has {cols['keys'].nbytes} bytes, expected {n} x {schema.key_row}")
+    elif schema.key_row:
         n = cols["keys"].nbytes // schema.key_row
     else:
         n = cols["values"].nbytes // max(schema.value_row, 1)
@@ -72,7 +86,19 @@ def _check_cols(schema: RecordSchema, cols: Dict[str, torch.Tensor]) -> int:
 
 
 def _columns(cols: Dict[str, torch.Tensor]) -> A.Columns:
-    return A.Columns(*[_ptr(cols.get(k)) for k in COLS])
+    """rh_columns of device tensors.  For a 'var' schema the returned object owns what its `values`
+    points to (the host descriptor and a padded heap copy): keep THIS object alive for the call --
+    a copy of the struct (an assignment into a ctypes array) does not."""
+    c = A.Columns(*[_ptr(cols.get(k)) for k in COLS])
+    offs = cols.get(VAR_OFFSETS)
+    if offs is not None:  # a 'var' schema: values -> the descriptor of heap + offsets (rh_var_values)
+        heap = cols["values"]
+        if heap.numel() % 4:  # the kernels read whole dwords: pad the heap, as lift_encoded does
+            heap = torch.cat([heap, torch.zeros(4 - heap.numel() % 4, dtype=torch.uint8, device=heap.device)])
+        var = A.VarValues(_ptr(heap), _ptr(offs), heap.numel())
+        c.values = C.addressof(var)
+        c._held = (var, heap)  # alive as long as the Columns
+    return c
 
 
 def lift_records(schema: RecordSchema, cols: Dict[str, torch.Tensor], block_sums: bool = True,

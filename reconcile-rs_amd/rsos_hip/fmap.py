@@ -54,6 +54,13 @@ def encode_row(schema: RecordSchema, value) -> Tuple[bytes, int, int, int, int]:
     if schema.record_kind == A.REC_PLAIN and (e.tombstone or e.phys or e.logical or e.node):
         raise ValueError("a plain map's values carry no stamp or state")
     vr = schema.value_row
+    if schema.is_var:  # bytes (or a str's UTF-8) of any length; a tombstone carries none
+        if e.tombstone and e.value not in (b"", "", None):
+            raise ValueError("a tombstone carries no value bytes")
+        if isinstance(e.value, int):
+            raise ValueError("an integer value needs a u32 / u64 value column")
+        vb = b"" if e.tombstone else (e.value.encode() if isinstance(e.value, str) else bytes(e.value))
+        return vb, e.phys, e.logical, e.node, 1 if e.tombstone else 0
     if e.tombstone:
         if e.value not in (b"", 0, None):
             raise ValueError("a tombstone carries no value bytes")
@@ -79,12 +86,14 @@ class _Rows:
     def clear(self):
         self.keys, self.vals, self.tags, self.ops = bytearray(), bytearray(), bytearray(), bytearray()
         self.phys, self.logical, self.node = [], [], []
+        self.offs = [0]  # a 'var' schema: vals is the ragged heap, row i = vals[offs[i]:offs[i + 1]]
         self.n = 0
 
     def add(self, kb: bytes, row, op: int):
         vb, ph, lg, nd, tag = row
         self.keys += kb
         self.vals += vb
+        self.offs.append(len(self.vals))
         self.tags.append(tag)
         self.ops.append(op)
         if self.s.dated_kind:
@@ -107,6 +116,10 @@ class _Rows:
         ops = np.frombuffer(bytes(self.ops), np.uint8)
         ptr = lambda k: None if held.get(k) is None else held[k].ctypes.data  # noqa: E731
         cols = A.Columns(*[ptr(k) for k in ("keys", "phys", "logical", "node", "tags", "values")])
+        if s.is_var:
+            heap, offs = np.frombuffer(bytes(self.vals), np.uint8), np.array(self.offs, np.uint64)
+            var = A.VarValues(heap.ctypes.data, offs.ctypes.data, heap.size)
+            cols.values = C.addressof(var)
         A.check(A.lib().rh_store_stage(store._h, C.byref(cols), ops.ctypes.data, n), "rh_store_stage")
         self.clear()
 

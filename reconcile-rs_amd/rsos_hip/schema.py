@@ -23,7 +23,8 @@ class RecordSchema:
     # ---- constructors for the reference's record types -------------------------------
     @staticmethod
     def plain(key: str, value: str) -> "RecordSchema":
-        """FingerprintTreeMap<K, V>: lift(k, v).  key/value: 'u32', 'u64', 'bytesN'."""
+        """FingerprintTreeMap<K, V>: lift(k, v).  key/value: 'u32', 'u64', 'bytesN'; value 'var':
+        Vec<u8> / String of a length that differs per record (a heap and offsets, VAL_VARBYTES)."""
         kk, kl = _kind(key, True)
         vk, vl = _kind(value, False)
         return RecordSchema(kk, kl, vk, vl, A.REC_PLAIN)
@@ -55,6 +56,11 @@ class RecordSchema:
         return {A.VAL_UNIT: 0, A.VAL_U32: 4, A.VAL_U64: 8}.get(self.value_kind, self.value_len)
 
     @property
+    def is_var(self) -> bool:
+        """Values are byte strings of per-record length: columns `values` (the heap) + `value_offsets`."""
+        return self.value_kind == A.VAL_VARBYTES
+
+    @property
     def dated_kind(self) -> bool:
         return self.record_kind == A.REC_DATED
 
@@ -77,6 +83,10 @@ def _kind(name: str, key: bool):
         return (A.KEY_U32 if key else A.VAL_U32), 4
     if name == "u64":
         return (A.KEY_U64 if key else A.VAL_U64), 8
+    if name == "var":
+        if key:
+            raise ValueError("keys are fixed-width: 'var' is a value kind")
+        return A.VAL_VARBYTES, 0
     if name.startswith("bytes"):
         return (A.KEY_BYTES if key else A.VAL_BYTES), int(name[5:])
     raise ValueError(f"unknown field kind {name!r}")

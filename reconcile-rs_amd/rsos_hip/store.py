@@ -111,11 +111,35 @@ class GpuFingerprintStore:
                 raise ValueError(f"unknown column {k!r}")
         return A.Columns(*[_np_ptr(held.get(k)) for k in HOST_COLS]), held
 
+    def _host_columns(self, cols: Dict[str, np.ndarray]) -> Tuple[A.Columns, Dict[str, np.ndarray]]:
+        """_columns for this store's schema.  A 'var' schema's values are two host arrays: `values`
+        (the uint8 heap, any alignment) and `value_offsets` (uint64, n + 1 entries; value i =
+        heap[offsets[i]:offsets[i + 1]]); both may be left out of a delete-only batch."""
+        if not self.schema.is_var:
+            return self._columns(cols)
+        cols = dict(cols)
+        heap, offs = cols.pop("values", None), cols.pop("value_offsets", None)
+        c, held = self._columns(cols)
+        if offs is not None:
+            heap = np.ascontiguousarray(np.zeros(0, np.uint8) if heap is None else heap, dtype=np.uint8).reshape(-1)
+            offs = np.ascontiguousarray(offs, dtype=np.uint64).reshape(-1)
+            var = A.VarValues(heap.ctypes.data, offs.ctypes.data, heap.size)
+            held["values"], held["value_offsets"], held["_var"] = heap, offs, var
+            c.values = C.addressof(var)
+        elif heap is not None:
+            raise ValueError("a 'var' schema's values need value_offsets")
+        return c, held
+
     # ---- fill ----------------------------------------------------------------------------
     def load_bulk(self, cols: Dict[str, np.ndarray]) -> None:
         """Replace the contents with records sorted by key, without duplicates."""
-        c, held = self._columns(cols)
-        n = len(held["keys"]) if "keys" in held else len(held["values"])
+        c, held = self._host_columns(cols)
+        if self.schema.is_var:
+            if "value_offsets" not in held:
+                raise ValueError("a 'var' schema's load needs columns 'values' and 'value_offsets'")
+            n = len(held["value_offsets"]) - 1
+        else:
+            n = len(held["keys"]) if "keys" in held else len(held["values"])
         A.check(self._f("load")(self._h, C.byref(c), n), "rh_store_load")
 
     def load_bulk_device(self, cols) -> None:
@@ -149,9 +173,11 @@ class GpuFingerprintStore:
         cols = (A.Columns * max(k, 1))()
         ns = (C.c_size_t * max(k, 1))()
         optr = (C.c_void_p * max(k, 1))()
+        keep = []  # the array holds copies of the structs: what a 'var' batch's values point to lives here
         for i, b in enumerate(batches):
             ns[i] = _check_cols(self.schema, b)
-            cols[i] = _columns(b)
+            keep.append(_columns(b))
+            cols[i] = keep[-1]
             o = None if ops is None else ops[i]
             if o is not None and (o.numel() != ns[i] or not o.is_cuda):
                 raise ValueError("ops must be m device bytes")
@@ -159,6 +185,7 @@ class GpuFingerprintStore:
         out = (C.c_uint64 * (3 * max(k, 1)))()
         A.check(self._f("apply_device_many")(self._h, cols, None if ops is None else optr, ns, k, out,
                                                    _torch_stream()), "rh_store_apply_device_many")
+        del keep  # (the call is synchronous)
         return [(int(out[3 * i]), int(out[3 * i + 1]), int(out[3 * i + 2])) for i in range(k)]
 
     def compact(self) -> None:
@@ -202,7 +229,7 @@ class GpuFingerprintStore:
     def stage(self, cols: Dict[str, np.ndarray], ops: np.ndarray) -> None:
         """Queue host rows (rh_store_stage): applied as one batch by the next call that reads the
         store; a key staged more than once keeps its last operation."""
-        c, held = self._columns(cols)
+        c, held = self._host_columns(cols)
         ops_a = np.ascontiguousarray(ops, dtype=np.uint8)
         A.check(self._f("stage")(self._h, C.byref(c), _np_ptr(ops_a), len(ops_a)), "rh_store_stage")
 
@@ -332,7 +359,7 @@ class GpuFingerprintStore:
 
     def apply(self, cols: Dict[str, np.ndarray], ops: np.ndarray) -> Tuple[int, int, int]:
         """Batched insert (op 0) / delete (op 1); returns (new, overwritten, deleted)."""
-        c, held = self._columns(cols)
+        c, held = self._host_columns(cols)
         ops_a = np.ascontiguousarray(ops, dtype=np.uint8)
         a, b, d = C.c_uint64(), C.c_uint64(), C.c_uint64()
         A.check(self._f("apply")(self._h, C.byref(c), _np_ptr(ops_a), len(ops_a), C.byref(a), C.byref(b),
@@ -344,7 +371,11 @@ class GpuFingerprintStore:
         """Insert-or-overwrite one record; True if the key was new (Rsos::insert returns the old V)."""
         s = self.schema
         cols = {"keys": np.frombuffer(self._key_bytes(key), np.uint8).copy()}
-        if s.value_row:
+        if s.is_var:
+            v = value.encode() if isinstance(value, str) else bytes(value)
+            cols["values"] = np.frombuffer(v, np.uint8).copy()
+            cols["value_offsets"] = np.array([0, len(v)], np.uint64)
+        elif s.value_row:
             v = value if isinstance(value, (bytes, bytearray)) else int(value).to_bytes(s.value_row, "little")
             if len(v) != s.value_row:
                 raise ValueError(f"value must be {s.value_row} bytes")

@@ -18,6 +18,7 @@ pub const RH_VAL_UNIT: i32 = 0;
 pub const RH_VAL_U32: i32 = 1;
 pub const RH_VAL_U64: i32 = 2;
 pub const RH_VAL_BYTES: i32 = 3;
+pub const RH_VAL_VARBYTES: i32 = 4;
 pub const RH_REC_PLAIN: i32 = 0;
 pub const RH_REC_DATED: i32 = 1;
 pub const RH_REC_PROJECTION: i32 = 2;
@@ -42,6 +43,15 @@ pub struct rh_columns {
     pub node: *const u64,
     pub tags: *const u8,
     pub values: *const c_void,
+}
+
+/// What `rh_columns.values` points to for `RH_VAL_VARBYTES`: value i = bytes[offsets[i] .. offsets[i + 1]).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct rh_var_values {
+    pub bytes: *const u8,
+    pub offsets: *const u64,
+    pub bytes_len: u64,
 }
 
 #[repr(C)]

@@ -96,7 +96,9 @@ pub struct RecordRow {
     pub tombstone: bool,
 }
 
-/// A value type whose canonical encoding the device synthesises from fixed-width columns.
+/// A value type whose canonical encoding the device synthesises from columns: fixed-width ones, or
+/// (`VALUE_KIND` = `RH_VAL_VARBYTES`, `VALUE_LEN` = 0: `String` / `Vec<u8>` values) a fixed-width key
+/// with a value of any length per record.
 /// Implemented in this crate (values.rs) for `lww_register::Entry<Timestamp, V>` (RECORD_KIND =
 /// DATED) and `State<V>` (PROJECTION) over any `V: FixedValue`, and for plain `u32` / `u64` /
 /// `FixedBytes<N>` values (PLAIN).  `write` must produce exactly the fields `rsos::encoding` would
@@ -171,6 +173,10 @@ fn schema<K: GpuKey, V: GpuRecord>() -> ffi::rh_schema {
 struct Batch {
     keys: Vec<u8>,
     values: Vec<u8>,
+    /// VARBYTES: `values` is the ragged heap, row i = values[offsets[i] .. offsets[i + 1]), and
+    /// `var` the descriptor `columns()` points the library at
+    offsets: Vec<u64>,
+    var: Option<ffi::rh_var_values>,
     phys: Vec<u64>,
     logical: Vec<u32>,
     node: Vec<u64>,
@@ -179,7 +185,9 @@ struct Batch {
 
 impl Batch {
     fn new<'a, K: GpuKey + 'a, V: GpuRecord + 'a>(items: impl Iterator<Item = (&'a K, Option<&'a V>)>) -> Batch {
-        let mut b = Batch { keys: vec![], values: vec![], phys: vec![], logical: vec![], node: vec![], tags: vec![] };
+        let var = V::VALUE_KIND == ffi::RH_VAL_VARBYTES;
+        let mut b = Batch { keys: vec![], values: vec![], offsets: vec![0], var: None, phys: vec![], logical: vec![],
+                            node: vec![], tags: vec![] };
         for (k, v) in items {
             b.keys.extend(k.column_bytes());
             let mut row = RecordRow::default();
@@ -188,7 +196,10 @@ impl Batch {
                     v.write(&mut row);
                     // a present value must fill the value column exactly: padding or truncating it
                     // would hash some other record and reconcile silently wrongly (rsos_trait.rs:54-56)
-                    if !row.tombstone {
+                    if var {
+                        // any length; a tombstone's row is empty (its span would be ignored anyway)
+                        assert!(!row.tombstone || row.value.is_empty(), "rsos-hip: a tombstone row carries no value bytes");
+                    } else if !row.tombstone {
                         assert_eq!(row.value.len(), V::VALUE_LEN as usize,
                                    "rsos-hip: GpuRecord::write produced a {}-byte value for a {}-byte value column",
                                    row.value.len(), V::VALUE_LEN);
@@ -200,10 +211,16 @@ impl Batch {
                 None => row.value = vec![0; V::VALUE_LEN as usize], // a delete: the value columns are ignored
             }
             b.values.extend(&row.value);
+            b.offsets.push(b.values.len() as u64);
             b.phys.push(row.phys);
             b.logical.push(row.logical);
             b.node.push(row.node);
             b.tags.push(row.tombstone as u8);
+        }
+        if var {
+            // (the vectors' buffers do not move with the Batch; the descriptor is read in place)
+            b.var = Some(ffi::rh_var_values { bytes: b.values.as_ptr(), offsets: b.offsets.as_ptr(),
+                                              bytes_len: b.values.len() as u64 });
         }
         b
     }
@@ -214,7 +231,10 @@ impl Batch {
             logical: self.logical.as_ptr(),
             node: self.node.as_ptr(),
             tags: self.tags.as_ptr(),
-            values: self.values.as_ptr() as *const c_void,
+            values: match &self.var {
+                Some(v) => v as *const ffi::rh_var_values as *const c_void,
+                None => self.values.as_ptr() as *const c_void,
+            },
         }
     }
 }

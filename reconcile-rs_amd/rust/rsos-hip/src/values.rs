@@ -10,8 +10,11 @@
 //!   column (the variant word is synthesised on the device);
 //! * `v`: a `u32` / `u64` is its LE bytes (value kinds U32 / U64, no prefix); a byte string
 //!   (`Vec<u8>`, `String`, `[u8; N]`, `FixedBytes<N>`) is a u64 length prefix then the bytes
-//!   (encoding/serializer.rs:105-113, :162-179) -> value kind BYTES, the prefix synthesised.
-//! A value whose byte length differs from the map's value column is a panic, never a padded row:
+//!   (encoding/serializer.rs:105-113, :162-179) -> value kind BYTES, the prefix synthesised;
+//!   a `Vec<u8>` / `String` itself, whose length differs per record -> value kind VARBYTES: the
+//!   batch's values packed in one heap with n + 1 offsets (`ffi::rh_var_values`), the prefix
+//!   synthesised from each value's length.
+//! A value whose byte length differs from a fixed-width map's value column is a panic, never a padded row:
 //! a padded row would hash some other record and reconcile silently wrongly (rsos_trait.rs:54-56).
 
 use lww_register::{Entry, State, Timestamp};
@@ -19,11 +22,13 @@ use serde::{Deserialize, Deserializer, Serialize, Serializer};
 
 use crate::{ffi, GpuRecord, RecordRow};
 
-/// A value type the device hashes from one fixed-width column.
+/// A value type the device hashes from one value column: fixed-width, or (VARBYTES) a heap of
+/// byte strings of per-record length.
 pub trait FixedValue: Serialize {
-    /// `RH_VAL_U32`, `RH_VAL_U64` or `RH_VAL_BYTES`
+    /// `RH_VAL_U32`, `RH_VAL_U64`, `RH_VAL_BYTES` or `RH_VAL_VARBYTES`
     const KIND: i32;
-    /// Bytes of the value column (for BYTES: the byte string's length, without its prefix).
+    /// Bytes of the value column (for BYTES: the byte string's length, without its prefix; 0 for
+    /// VARBYTES, whose lengths travel as offsets).
     const LEN: u32;
     /// Append the column bytes: LE integers, or the byte string without its length prefix.
     fn column(&self, out: &mut Vec<u8>);
@@ -51,6 +56,26 @@ impl FixedValue for () {
     const KIND: i32 = ffi::RH_VAL_UNIT;
     const LEN: u32 = 0;
     fn column(&self, _out: &mut Vec<u8>) {}
+}
+
+// `Vec<u8>` and `String` (a sequence of u8 / a str: u64 length then the bytes,
+// encoding/serializer.rs:105-113): the VARBYTES value kind, any length per record.  So
+// `HipFingerprintMap<u64, String>` and `HipFingerprintMap<[u8; 16], Entry<Timestamp, Vec<u8>>>`
+// are column-store maps with device key search, rounds and the host tier -- no encoded store.
+impl FixedValue for Vec<u8> {
+    const KIND: i32 = ffi::RH_VAL_VARBYTES;
+    const LEN: u32 = 0;
+    fn column(&self, out: &mut Vec<u8>) {
+        out.extend_from_slice(self);
+    }
+}
+
+impl FixedValue for String {
+    const KIND: i32 = ffi::RH_VAL_VARBYTES;
+    const LEN: u32 = 0;
+    fn column(&self, out: &mut Vec<u8>) {
+        out.extend_from_slice(self.as_bytes());
+    }
 }
 
 // serde serialises [u8; N] (N <= 32) as a tuple: rsos's canonical Serializer writes the tuple's
@@ -168,7 +193,7 @@ macro_rules! plain_record {
         }
     )*};
 }
-plain_record!(u32 u64);
+plain_record!(u32 u64 String Vec<u8>);
 
 impl<const N: usize> GpuRecord for FixedBytes<N> {
     const VALUE_KIND: i32 = ffi::RH_VAL_BYTES;
