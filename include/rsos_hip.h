@@ -59,8 +59,38 @@ typedef enum rh_status {
  *   U32   : u32 / i32       -> 4 bytes LE              (:76-79)
  *   U64   : u64 / i64/usize -> 8 bytes LE              (:81-84)
  *   BYTES : [u8; L] / Vec<u8> / String of fixed byte length L
- *                           -> u64 LE length L, then the L bytes (:105-113,162-179)        */
-typedef enum rh_key_kind { RH_KEY_UNIT = 0, RH_KEY_U32 = 1, RH_KEY_U64 = 2, RH_KEY_BYTES = 3 } rh_key_kind;
+ *                           -> u64 LE length L, then the L bytes (:105-113,162-179)
+ *   STR   : String / Vec<u8> / &str of a length that differs per key, at most W - 1 bytes,
+ *           held in a row of W = schema.key_len bytes (16 or 32; any other width: RH_ERR_ARG)
+ *                           -> u64 LE length L, then the L bytes (:105-113): the string's
+ *                              encoding, not the row's
+ *
+ * A STR key row holds the string's L bytes (L <= W - 1), zero bytes up to offset W - 2, and
+ * row[W - 1] = L.  memcmp over two such rows orders them as Ord of String / Vec<u8> / &[u8] orders
+ * the strings: lexicographic bytes decide first, as they do for the strings; a proper prefix comes
+ * first, since the padding is the minimum byte and so the longer string is >= on every padded
+ * position; and two strings that tie over all W - 1 bytes (they differ only in trailing zero bytes)
+ * are ordered by L in the last byte, the shorter first.  So a store treats the rows as RH_KEY_BYTES
+ * rows of width W everywhere except in the lift: rh_store_rank*, _select, _keys, _aggregate_keys,
+ * _resolve_segments, _split_segments, _protocol_round and the host tier work on them unchanged,
+ * and every key argument and key result of those calls is a row in this form.  Host-column calls
+ * (rh_store_load / _apply / _stage) validate every key row -- length byte <= W - 1, zero padding --
+ * and return RH_ERR_ARG naming the row, with the store unchanged, before any device work.  Question
+ * keys (ranks, range bounds, segment bounds) are only compared and are not validated: a malformed
+ * one is ordered as its bytes say.  In a DEVICE key column, nonzero padding or a length byte above
+ * W - 1 is a caller error that gives a wrong fingerprint, never an out-of-range access (the lift
+ * clips the length and masks the padding).
+ * Values under STR keys: RH_VAL_VARBYTES only (String -> String, String -> Vec<u8>; PLAIN, DATED
+ * and PROJECTION records, tag column optional); any other value kind is RH_ERR_UNSUPPORTED with a
+ * message that names RH_KEY_STR.  Strings of 32 bytes or more stay with the encoded store
+ * (rh_estore_*): a 64-byte row would need sort / search / merge instantiations of its own.       */
+typedef enum rh_key_kind {
+    RH_KEY_UNIT = 0,
+    RH_KEY_U32 = 1,
+    RH_KEY_U64 = 2,
+    RH_KEY_BYTES = 3,
+    RH_KEY_STR = 4
+} rh_key_kind;
 /* Value encodings: UNIT / U32 / U64 as the keys'; BYTES: a byte string of one length per map (value_len),
  * u64 LE length then the bytes; VARBYTES: Vec<u8> / String / &str of a length that differs per
  * record -- u64 LE length, then the bytes (:105-113) -- given as a heap and offsets (rh_var_values
@@ -135,11 +165,15 @@ typedef struct rh_aggregate {
 int         rh_abi_version(void);
 const char *rh_last_error(void);
 /* 1 if a specialised kernel exists for this schema, 0 if it needs the encoded path, <0 bad.
- * VARBYTES values: 1 with unit, u32, u64, 16- and 32-byte keys, 0 with any other key length.   */
+ * VARBYTES values: 1 with unit, u32, u64, 16- and 32-byte keys, 0 with any other key length.
+ * STR keys: 1 for (STR, 16 | 32, VARBYTES); RH_ERR_ARG for STR with any other key_len; 0 for
+ * STR with any other value kind.                                                               */
 int         rh_schema_supported(const rh_schema *schema);
 /* canonical-encoding length of a present / tombstone record of this schema (host helper).
  * VARBYTES values: the length of a present record with an EMPTY value -- the prefix the value's
- * bytes follow (key, stamp, State variant, the value's u64 length); the tombstone length as ever. */
+ * bytes follow (key, stamp, State variant, the value's u64 length); the tombstone length as ever.
+ * STR keys: both lengths are those of the EMPTY key (its u64 length alone) -- 8 + stamp + variant
+ * + 8 for a present record with an empty value; add L for a key of L bytes.                     */
 int64_t     rh_schema_record_len(const rh_schema *schema, int tombstone);
 
 /* ---- device-resident batch API (all pointers are device pointers) -------------------- */
@@ -455,6 +489,9 @@ int rh_store_load_snapshot(rh_store *dated, rh_store *projection, int key_form, 
  * 1 = Included, then the key), end bound (0 = Unbounded, 1 = Excluded, then the key), the 32
  * fingerprint bytes (rsos/src/fingerprint.rs:74-83), the size as a varint.  Keys: u32 / u64
  * varint, [u8; L] raw bytes (RH_FORM_ARRAY), Vec<u8> varint length + bytes (RH_FORM_VEC).
+ * RH_KEY_STR keys are RH_FORM_VEC only (RH_FORM_ARRAY: RH_ERR_ARG): varint L, then the string's L
+ * bytes -- what Vec<u8> / String are under the gossip codec; the key arrays hold padded rows, and
+ * decoding a length of key_len or more is RH_ERR_DATA.
  * msg_tag >= 0 prefixes every item with that Message variant (0 = ComparisonItem,
  * 3 = ValueComparisonItem, src/replica.rs:184-199), giving the byte stream send_messages_to
  * packs into datagrams (src/replica/pacing.rs:200); msg_tag = -1 encodes bare items.

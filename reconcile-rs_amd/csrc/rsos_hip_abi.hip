@@ -179,16 +179,20 @@ int value_row(const rh_schema &s) {
     }
 }
 bool is_var(const rh_schema &s) { return s.value_kind == RH_VAL_VARBYTES; }
+// short string keys in fixed-width rows: RH_KEY_BYTES rows of that width to everything but the lift
+bool is_str(const rh_schema &s) { return s.key_kind == RH_KEY_STR; }
 const rh_var_values *var_of(const rh_columns &c) { return static_cast<const rh_var_values *>(c.values); }
 
 int check_schema(const rh_schema *s) {
     if (!s) return fail(RH_ERR_ARG, "schema is NULL");
-    if (s->key_kind < 0 || s->key_kind > 3) return fail(RH_ERR_ARG, "bad key_kind");
+    if (s->key_kind < 0 || s->key_kind > 4) return fail(RH_ERR_ARG, "bad key_kind");
     if (s->value_kind < 0 || s->value_kind > 4) return fail(RH_ERR_ARG, "bad value_kind");
     if (s->record_kind < 0 || s->record_kind > 2) return fail(RH_ERR_ARG, "bad record_kind");
     if (s->reserved != 0) return fail(RH_ERR_ARG, "schema.reserved must be 0");
     if (s->key_kind == RH_KEY_U32 && s->key_len != 4) return fail(RH_ERR_ARG, "u32 key needs key_len 4");
     if (s->key_kind == RH_KEY_U64 && s->key_len != 8) return fail(RH_ERR_ARG, "u64 key needs key_len 8");
+    if (s->key_kind == RH_KEY_STR && s->key_len != 16 && s->key_len != 32)
+        return fail(RH_ERR_ARG, "RH_KEY_STR needs key_len 16 or 32 (the row width: strings of up to 15 or 31 bytes)");
     if (s->value_kind == RH_VAL_U32 && s->value_len != 4) return fail(RH_ERR_ARG, "u32 value needs value_len 4");
     if (s->value_kind == RH_VAL_U64 && s->value_len != 8) return fail(RH_ERR_ARG, "u64 value needs value_len 8");
     if (s->value_kind == RH_VAL_VARBYTES && s->value_len != 0)
@@ -258,12 +262,45 @@ int check_var_host(const rh_schema &s, const rh_columns &h, size_t n) {
     return RH_OK;
 }
 
+// Host key rows of a RH_KEY_STR schema of row width w, checked before anything changes: the length
+// byte at most w - 1, zero bytes from the string's end to offset w - 2.  (Device columns are not
+// read back: there a malformed row is a wrong fingerprint, lift_str.hpp.)
+int check_str_host(bool str, size_t w, const rh_columns &h, size_t n) {
+    if (!str || n == 0 || !h.keys) return RH_OK;
+    const uint8_t *k = static_cast<const uint8_t *>(h.keys);
+    for (size_t i = 0; i < n; i++, k += w) {
+        const size_t len = k[w - 1];
+        if (len > w - 1)
+            return fail(RH_ERR_ARG, "RH_KEY_STR: key row " + std::to_string(i) + " has length byte " +
+                                        std::to_string(len) + " (at most " + std::to_string(w - 1) + ")");
+        for (size_t j = len; j + 1 < w; j++)
+            if (k[j]) return fail(RH_ERR_ARG, "RH_KEY_STR: key row " + std::to_string(i) + " has nonzero padding");
+    }
+    return RH_OK;
+}
+
 // dst_row (optional, single lift without block sums): record i's fingerprint to row dst_row[i]
 int lift_dispatch(const rh_schema &s, const rh_columns &c, size_t n, uint8_t *fps, uint8_t *bs,
                   uint8_t *fps2, uint8_t *bs2, bool dual, hipStream_t st, const uint32_t *dst_row = nullptr,
                   const uint32_t *dst2 = nullptr) {
     bool supported = false;
     if (dst_row && (bs || dual)) return fail(RH_ERR_STATE, "lift to sorted rows: no block sums (internal error)");
+    if (is_str(s)) {
+        if (!is_var(s))
+            return fail(RH_ERR_UNSUPPORTED, "RH_KEY_STR keys take RH_VAL_VARBYTES values only; canonical-encode on "
+                                            "the host and use rh_lift_encoded_async");
+        rh::VarCols dc = to_var_dev(s, c);
+        dc.dst = dst_row;
+        dc.dst2 = dst2;
+        // as for any VARBYTES schema: two launches per lift (lift_str.hpp), the dual lift two passes
+        const bool tags = c.tags != nullptr && s.record_kind != RH_REC_PLAIN;
+        hipError_t ev = rh::launch_lift_str((int)s.key_len, s.record_kind, tags, dc, n, fps, bs, st, &supported);
+        if (supported && ev == hipSuccess && dual)
+            ev = rh::launch_lift_str((int)s.key_len, RH_REC_PROJECTION, tags, dc, n, fps2, bs2, st, &supported);
+        if (!supported) return fail(RH_ERR_UNSUPPORTED, "RH_KEY_STR rows are 16 or 32 bytes wide");
+        if (ev != hipSuccess) return fail(RH_ERR_HIP, std::string("lift launch: ") + hipGetErrorString(ev));
+        return RH_OK;
+    }
     if (is_var(s)) {
         rh::VarCols dc = to_var_dev(s, c);
         dc.dst = dst_row;
@@ -448,6 +485,7 @@ int rh_schema_supported(const rh_schema *schema) {
     int rc = check_schema(schema);
     if (rc) return rc;
     const rh_schema &s = *schema;
+    if (is_str(s)) return is_var(s) && rh::str_key_supported(key_row(s)) ? 1 : 0;
     if (is_var(s)) return rh::var_key_supported(s.key_kind, key_row(s)) ? 1 : 0;
     return rh::schema_instantiated(s.key_kind, (int)s.key_len, s.value_kind, (int)s.value_len) ? 1 : 0;
 }
@@ -456,7 +494,8 @@ int64_t rh_schema_record_len(const rh_schema *schema, int tombstone) {
     int rc = check_schema(schema);
     if (rc) return rc;
     const rh_schema &s = *schema;
-    int64_t key = s.key_kind == RH_KEY_BYTES ? 8 + (int64_t)s.key_len : key_row(s);
+    // STR: the u64 length of an empty string (add L, the key's own length)
+    int64_t key = s.key_kind == RH_KEY_BYTES ? 8 + (int64_t)s.key_len : is_str(s) ? 8 : key_row(s);
     int64_t stamp = s.record_kind == RH_REC_DATED ? 20 : 0;
     if (s.record_kind == RH_REC_PLAIN) tombstone = 0;
     int64_t tag = s.record_kind == RH_REC_PLAIN ? 0 : 4;
@@ -825,6 +864,14 @@ struct PinnedAny {
 struct rh_store {
     int device = 0;
     rh_schema schema{};
+    // RH_KEY_STR: `schema` says RH_KEY_BYTES (what the rows are to every key operation); the lift
+    // alone is told the string kind
+    bool str_keys = false;
+    rh_schema lift_schema() const {
+        rh_schema l = schema;
+        if (str_keys) l.key_kind = RH_KEY_STR;
+        return l;
+    }
     hipStream_t stream = nullptr;
     std::mutex mu;  // serialises callers sharing one store (readers under a RwLock read guard)
     rh::StoreKeyOps *kops = nullptr;
@@ -2063,7 +2110,7 @@ struct rh_store {
         if (m) {
             RH_HIP(hipMemcpyAsync(bkeys[cb].p, c.keys, m * kl, hipMemcpyDeviceToDevice, stream));
             if (!lifted &&
-                (rc = lift_dispatch(schema, c, m, bfps[cb].p, bsums.p, nullptr, nullptr, false, stream)))
+                (rc = lift_dispatch(lift_schema(), c, m, bfps[cb].p, bsums.p, nullptr, nullptr, false, stream)))
                 return rc;
             RH_HIP(hipMemsetAsync(flag.p, 0, 4, stream));
             RH_HIP(kops->check_sorted(bkeys[cb].p, m, flag.p, stream));
@@ -2492,7 +2539,7 @@ struct rh_store {
             }
         }
         int rc;
-        if ((rc = lift_dispatch(schema, c, m, sfps.p, nullptr, nullptr, nullptr, false, stream, pos, sort_s2o)))
+        if ((rc = lift_dispatch(lift_schema(), c, m, sfps.p, nullptr, nullptr, nullptr, false, stream, pos, sort_s2o)))
             return rc;
         RH_HIP(kops->search_sampled(jb.keys, jb.n, jb.smp, jb.smp2, skeys.p, m, jb.rank, jb.present, stream, jb.tb));
         RH_HIP(kops->search_sampled(jd.keys, jd.n, jd.smp, jd.smp2, skeys.p, m, jd.rank, jd.present, stream, jd.tb));
@@ -3542,14 +3589,19 @@ int rh_store_create(int device, const rh_schema *schema, rh_store **out) {
     int rc = check_schema(schema);
     if (rc) return rc;
     if (!out) return fail(RH_ERR_ARG, "out is NULL");
+    if (is_str(*schema) && !is_var(*schema))
+        return fail(RH_ERR_UNSUPPORTED, "RH_KEY_STR keys take RH_VAL_VARBYTES values only (other maps with string "
+                                        "keys: the encoded store)");
     if (rh_schema_supported(schema) != 1)
         return fail(RH_ERR_UNSUPPORTED, "store needs a schema with a specialised lift kernel");
-    rh::StoreKeyOps *kops = rh::store_key_ops(schema->key_kind, key_row(*schema));
+    // string rows sort, search and merge as byte rows of their width
+    rh::StoreKeyOps *kops = rh::store_key_ops(is_str(*schema) ? RH_KEY_BYTES : schema->key_kind, key_row(*schema));
     if (!kops) return fail(RH_ERR_UNSUPPORTED, "store keys must be u32, u64 or 8/16/32-byte arrays");
     RH_HIP(hipSetDevice(device));
     rh_store *s = new rh_store();
     s->device = device;
     s->schema = *schema;
+    if (is_str(*schema)) s->schema.key_kind = RH_KEY_BYTES, s->str_keys = true;
     s->kops = kops;
     s->kl = key_row(*schema);
     hipError_t e = create_fore_stream(&s->stream);
@@ -3577,6 +3629,7 @@ int rh_store_load(rh_store *s, const rh_columns *h, size_t n) {
     if (!s || !h) return fail(RH_ERR_ARG, "NULL");
     int rc;
     if ((rc = check_var_host(s->schema, *h, n))) return rc;
+    if ((rc = check_str_host(s->str_keys, s->kl, *h, n))) return rc;
     RH_LOCK_NOFLUSH(s);
     s->pend.clear();  // a load replaces the contents: staged rows before it are superseded
     if ((rc = s->staging.upload(s->schema, *h, n, s->stream))) return rc;
@@ -3952,6 +4005,7 @@ int rh_store_stage(rh_store *s, const rh_columns *h, const uint8_t *ops, size_t 
     for (size_t i = 0; i < m; i++)
         if (ops[i] > 1) return fail(RH_ERR_ARG, "op must be 0 (insert) or 1 (delete)");
     if (int rc = check_var_host(sc, *h, m)) return rc;
+    if (int rc = check_str_host(s->str_keys, s->kl, *h, m)) return rc;
     std::lock_guard<std::mutex> g(s->mu);
     if (s->pend.n + m >= (1ull << 31)) return fail(RH_ERR_ARG, "pending batch limit (2^31 rows) exceeded");
     try {
@@ -4005,6 +4059,7 @@ int rh_store_apply(rh_store *s, const rh_columns *h, const uint8_t *ops, size_t 
     if (!s || !h || (m && !ops)) return fail(RH_ERR_ARG, "NULL");
     int rc;
     if ((rc = check_var_host(s->schema, *h, m))) return rc;
+    if ((rc = check_str_host(s->str_keys, s->kl, *h, m))) return rc;
     RH_LOCK(s);
     uint64_t c[3];
     if ((rc = s->apply_host(*h, ops, m, c))) return rc;

@@ -86,6 +86,11 @@ struct KeyCodec {
     void put(Writer &w, const uint8_t *k) const {
         if (kind == RH_KEY_U32) { uint32_t v; memcpy(&v, k, 4); w.varint(v); }
         else if (kind == RH_KEY_U64) { uint64_t v; memcpy(&v, k, 8); w.varint(v); }
+        else if (kind == RH_KEY_STR) {  // the string in the row: varint L, then its L bytes
+            const size_t l = k[kl - 1] < kl - 1 ? k[kl - 1] : kl - 1;
+            w.varint(l);
+            w.raw(k, l);
+        }
         else {
             if (form == RH_FORM_VEC) w.varint(kl);
             w.raw(k, kl);
@@ -105,6 +110,17 @@ struct KeyCodec {
             memcpy(k, &v, 8);
             return RD_OK;
         }
+        if (kind == RH_KEY_STR) {  // into the padded row (zeroed by the caller), L in its last byte
+            if ((s = r.varint(&v, ~0ull, "key length"))) return s;
+            if (v > kl - 1) {
+                r.why = "key length " + std::to_string(v) + " exceeds the " + std::to_string(kl - 1) +
+                        " bytes a RH_KEY_STR row of " + std::to_string(kl) + " holds";
+                return RD_BAD;
+            }
+            if ((s = r.raw(k, (size_t)v))) return s;
+            k[kl - 1] = (uint8_t)v;
+            return RD_OK;
+        }
         if (form == RH_FORM_VEC) {
             if ((s = r.varint(&v, ~0ull, "key length"))) return s;
             if (v != kl) {
@@ -122,6 +138,10 @@ int key_codec(const rh_schema *s, int form, KeyCodec *kc) {
     if (s->key_kind == RH_KEY_U32 && s->key_len == 4 && form == RH_FORM_ARRAY) *kc = {RH_KEY_U32, form, 4};
     else if (s->key_kind == RH_KEY_U64 && s->key_len == 8 && form == RH_FORM_ARRAY) *kc = {RH_KEY_U64, form, 8};
     else if (s->key_kind == RH_KEY_BYTES && s->key_len > 0) *kc = {RH_KEY_BYTES, form, s->key_len};
+    else if (s->key_kind == RH_KEY_STR && (s->key_len == 16 || s->key_len == 32) && form == RH_FORM_VEC)
+        *kc = {RH_KEY_STR, form, s->key_len};
+    else if (s->key_kind == RH_KEY_STR)
+        return rh::set_error(RH_ERR_ARG, "RH_KEY_STR wire keys are Vec<u8> / String: RH_FORM_VEC, key_len 16 or 32");
     else return rh::set_error(RH_ERR_ARG, "wire keys must be u32, u64 or byte strings (RH_FORM_VEC only for bytes)");
     return RH_OK;
 }

@@ -23,10 +23,12 @@ from .device import (lift_records, lift_dual, lift_encoded, lift_fixed, reduce_b
                      combine_aggregates, block_sums_for)
 from .store import GpuFingerprintStore
 from .fmap import Entry, FingerprintMap
+from .strkeys import pack_str_keys, unpack_str_keys
 from ._abi import RsosHipError, lib
 
 __all__ = [
     "Aggregate", "Fingerprint", "RecordSchema", "lift_records", "lift_dual", "lift_encoded", "lift_fixed",
     "reduce_blocks", "range_aggregates", "combine_aggregates", "block_sums_for",
     "GpuFingerprintStore", "FingerprintMap", "Entry", "RsosHipError", "lib",
+    "pack_str_keys", "unpack_str_keys",
 ]

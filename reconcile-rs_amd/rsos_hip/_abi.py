@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(HERE, "_lib", "librsos_hip.so")
 # rh_status
 OK, ERR_ARG, ERR_HIP, ERR_OOM, ERR_UNSUPPORTED, ERR_STATE, ERR_DATA = 0, -1, -2, -3, -4, -5, -6
 # schema enums (rsos_hip.h)
-KEY_UNIT, KEY_U32, KEY_U64, KEY_BYTES = 0, 1, 2, 3
+KEY_UNIT, KEY_U32, KEY_U64, KEY_BYTES, KEY_STR = 0, 1, 2, 3, 4
 VAL_UNIT, VAL_U32, VAL_U64, VAL_BYTES, VAL_VARBYTES = 0, 1, 2, 3, 4
 REC_PLAIN, REC_DATED, REC_PROJECTION = 0, 1, 2
 BLOCK, SUPER = 256, 65536

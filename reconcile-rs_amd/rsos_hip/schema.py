@@ -24,7 +24,9 @@ class RecordSchema:
     @staticmethod
     def plain(key: str, value: str) -> "RecordSchema":
         """FingerprintTreeMap<K, V>: lift(k, v).  key/value: 'u32', 'u64', 'bytesN'; value 'var':
-        Vec<u8> / String of a length that differs per record (a heap and offsets, VAL_VARBYTES)."""
+        Vec<u8> / String of a length that differs per record (a heap and offsets, VAL_VARBYTES);
+        key 'str15' / 'str31': String / Vec<u8> of at most 15 / 31 bytes in a 16- / 32-byte row
+        (KEY_STR, strkeys.pack_str_keys), with 'var' values."""
         kk, kl = _kind(key, True)
         vk, vl = _kind(value, False)
         return RecordSchema(kk, kl, vk, vl, A.REC_PLAIN)
@@ -61,6 +63,11 @@ class RecordSchema:
         return self.value_kind == A.VAL_VARBYTES
 
     @property
+    def is_str(self) -> bool:
+        """Keys are short strings packed in fixed-width rows (strkeys.pack_str_keys)."""
+        return self.key_kind == A.KEY_STR
+
+    @property
     def dated_kind(self) -> bool:
         return self.record_kind == A.REC_DATED
 
@@ -87,6 +94,10 @@ def _kind(name: str, key: bool):
         if key:
             raise ValueError("keys are fixed-width: 'var' is a value kind")
         return A.VAL_VARBYTES, 0
+    if name in ("str15", "str31"):  # named by the longest string; the row is one byte wider
+        if not key:
+            raise ValueError("'str15' / 'str31' are key kinds: a string value is 'var'")
+        return A.KEY_STR, int(name[3:]) + 1
     if name.startswith("bytes"):
         return (A.KEY_BYTES if key else A.VAL_BYTES), int(name[5:])
     raise ValueError(f"unknown field kind {name!r}")

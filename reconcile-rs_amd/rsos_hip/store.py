@@ -13,7 +13,8 @@ Keys and fingerprints are held in rank order in HBM with the block / super-block
 select and range bounds are answered on the device.  Record payloads are lifted on ingest and
 not kept on the device (the caller owns K and V, as the reference's map does).  Keys are
 fixed-width: bytes of schema.key_len for byte keys (memcmp order = Ord of [u8; L]), ints for
-u32/u64 keys.
+u32/u64 keys; 'str15' / 'str31' keys are given as str (UTF-8) or bytes and come back as bytes
+(strkeys.py: the padded rows' memcmp order = Ord of String).
 """
 from __future__ import annotations
 
@@ -25,8 +26,9 @@ import numpy as np
 from . import _abi as A
 from .fingerprint import Aggregate
 from .schema import RecordSchema
+from .strkeys import pack_str_keys, unpack_str_keys
 
-Key = Union[bytes, int]
+Key = Union[bytes, int, str]
 HOST_COLS = ("keys", "phys", "logical", "node", "tags", "values")
 
 
@@ -93,6 +95,8 @@ class GpuFingerprintStore:
             return int(k).to_bytes(4, "little")
         if s.key_kind == A.KEY_U64:
             return int(k).to_bytes(8, "little")
+        if s.is_str:  # str (UTF-8) or bytes of at most key_row - 1 bytes, as its padded row
+            return pack_str_keys([k], s.key_row).tobytes()
         b = bytes(k)
         if len(b) != s.key_row:
             raise ValueError(f"key must be {s.key_row} bytes")
@@ -101,7 +105,12 @@ class GpuFingerprintStore:
     def _key_out(self, b: bytes) -> Key:
         if self.schema.key_kind in (A.KEY_U32, A.KEY_U64):
             return int.from_bytes(b, "little")
+        if self.schema.is_str:  # the string's bytes (a key need not be UTF-8)
+            return unpack_str_keys(np.frombuffer(b, np.uint8).reshape(1, -1))[0]
         return b
+
+    def _same_key(self, a: Key, b: Key) -> bool:
+        return self._key_bytes(a) == self._key_bytes(b)  # (a string key may be given as str or bytes)
 
     @staticmethod
     def _columns(cols: Dict[str, np.ndarray]) -> Tuple[A.Columns, Dict[str, np.ndarray]]:
@@ -294,10 +303,10 @@ class GpuFingerprintStore:
         rng = rng or KeyRange.full()
         n = self.size()
         lo = 0 if rng.start is None else self.rank(rng.start)
-        if rng.start is not None and rng.start_kind == "excluded" and lo < n and self.select(lo) == rng.start:
+        if rng.start is not None and rng.start_kind == "excluded" and lo < n and self._same_key(self.select(lo), rng.start):
             lo += 1
         hi = n if rng.end is None else self.rank(rng.end)
-        if rng.end is not None and rng.end_kind == "included" and hi < n and self.select(hi) == rng.end:
+        if rng.end is not None and rng.end_kind == "included" and hi < n and self._same_key(self.select(hi), rng.end):
             hi += 1
         if hi <= lo:
             return

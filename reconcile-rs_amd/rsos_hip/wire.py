@@ -20,8 +20,9 @@ import numpy as np
 from . import _abi as A
 from .fingerprint import Aggregate
 from .schema import RecordSchema
+from .strkeys import pack_str_keys, unpack_str_keys
 
-Key = Union[bytes, int]
+Key = Union[bytes, int, str]
 COMPARISON_ITEM, VALUE_COMPARISON_ITEM = 0, 3
 _FORMS = {"array": A.FORM_ARRAY, "vec": A.FORM_VEC}
 
@@ -40,6 +41,8 @@ def _key_bytes(schema: RecordSchema, k: Key) -> bytes:
         return int(k).to_bytes(4, "little")
     if schema.key_kind == A.KEY_U64:
         return int(k).to_bytes(8, "little")
+    if schema.is_str:  # the padded row; on the wire (key_form 'vec') the string itself
+        return pack_str_keys([k], schema.key_row).tobytes()
     b = bytes(k)
     if len(b) != schema.key_row:
         raise ValueError(f"key must be {schema.key_row} bytes")
@@ -47,6 +50,8 @@ def _key_bytes(schema: RecordSchema, k: Key) -> bytes:
 
 
 def _key_out(schema: RecordSchema, b: bytes) -> Key:
+    if schema.is_str:
+        return unpack_str_keys(np.frombuffer(b, np.uint8).reshape(1, -1))[0]
     return int.from_bytes(b, "little") if schema.key_kind in (A.KEY_U32, A.KEY_U64) else b
 
 

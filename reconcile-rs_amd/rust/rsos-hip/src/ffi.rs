@@ -14,6 +14,7 @@ pub const RH_KEY_UNIT: i32 = 0;
 pub const RH_KEY_U32: i32 = 1;
 pub const RH_KEY_U64: i32 = 2;
 pub const RH_KEY_BYTES: i32 = 3;
+pub const RH_KEY_STR: i32 = 4;
 pub const RH_VAL_UNIT: i32 = 0;
 pub const RH_VAL_U32: i32 = 1;
 pub const RH_VAL_U64: i32 = 2;

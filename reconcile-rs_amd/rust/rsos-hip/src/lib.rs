@@ -23,17 +23,25 @@
 //! Errors: a non-zero status from the library is a bug or a device failure; the reference
 //! fails loudly on those (`lift` panics on an encoder failure, fingerprint.rs:240-246), so
 //! this crate panics with the library's message.
+//!
+//! String keys: `HipFingerprintMap<ShortString<32>, String>` (or `ShortString<16>`, and
+//! `Entry<Timestamp, String>` / `State<String>` values) is the column-store map of a reference
+//! `FingerprintTreeMap<String, String>` whose keys are at most 31 (15) bytes: same fingerprints,
+//! same order (`strkey.rs`, `RH_KEY_STR`), with rounds, staged inserts and the host tier as for any
+//! fixed-width key.  Keys of 32 bytes or more take [`HipEncodedMap`].
 
 mod encoded;
 mod ffi;
 mod round;
 mod sharded;
 mod sorted;
+mod strkey;
 mod values;
 
 pub use encoded::HipEncodedMap;
 pub use round::RoundPolicy;
 pub use sharded::HipShardedMap;
+pub use strkey::ShortString;
 pub use values::{FixedBytes, FixedValue};
 
 use std::ffi::CStr;
@@ -55,7 +63,8 @@ fn check(rc: i32, what: &str) {
 pub trait GpuKey: Ord + Clone + Serialize {
     const KIND: i32;
     const LEN: u32;
-    /// The key column bytes: LE integer for u32 / u64, the raw bytes for `[u8; N]`.
+    /// The key column bytes: LE integer for u32 / u64, the raw bytes for `[u8; N]`, the padded row
+    /// of a `ShortString<W>`.
     fn column_bytes(&self) -> Vec<u8>;
     /// The key of `LEN` column bytes (the inverse of `column_bytes`: keys the library returns).
     fn from_column_bytes(b: &[u8]) -> Self;
