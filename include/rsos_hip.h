@@ -61,16 +61,19 @@ typedef enum rh_status {
  *   BYTES : [u8; L] / Vec<u8> / String of fixed byte length L
  *                           -> u64 LE length L, then the L bytes (:105-113,162-179)
  *   STR   : String / Vec<u8> / &str of a length that differs per key, at most W - 1 bytes,
- *           held in a row of W = schema.key_len bytes (16 or 32; any other width: RH_ERR_ARG)
+ *           held in a row of W = schema.key_len bytes (16, 32 or 64: strings of at most 15, 31
+ *           or 63 bytes; any other width: RH_ERR_ARG)
  *                           -> u64 LE length L, then the L bytes (:105-113): the string's
  *                              encoding, not the row's
  *
  * A STR key row holds the string's L bytes (L <= W - 1), zero bytes up to offset W - 2, and
- * row[W - 1] = L.  memcmp over two such rows orders them as Ord of String / Vec<u8> / &[u8] orders
- * the strings: lexicographic bytes decide first, as they do for the strings; a proper prefix comes
- * first, since the padding is the minimum byte and so the longer string is >= on every padded
- * position; and two strings that tie over all W - 1 bytes (they differ only in trailing zero bytes)
- * are ordered by L in the last byte, the shorter first.  So a store treats the rows as RH_KEY_BYTES
+ * row[W - 1] = L: L <= 15 and row[15] = L at W = 16, L <= 31 and row[31] = L at W = 32, L <= 63 and
+ * row[63] = L at W = 64.  memcmp over two such rows orders them as Ord of String / Vec<u8> / &[u8]
+ * orders the strings, and the argument does not depend on W -- it holds for all three widths:
+ * lexicographic bytes decide first, as they do for the strings; a proper prefix comes first,
+ * since the padding is the minimum byte and so the longer string is >= on every padded position;
+ * and two strings that tie over all W - 1 bytes (they differ only in trailing zero bytes) are
+ * ordered by L in the last byte, the shorter first.  So a store treats the rows as RH_KEY_BYTES
  * rows of width W everywhere except in the lift: rh_store_rank*, _select, _keys, _aggregate_keys,
  * _resolve_segments, _split_segments, _protocol_round and the host tier work on them unchanged,
  * and every key argument and key result of those calls is a row in this form.  Host-column calls
@@ -82,8 +85,14 @@ typedef enum rh_status {
  * clips the length and masks the padding).
  * Values under STR keys: RH_VAL_VARBYTES only (String -> String, String -> Vec<u8>; PLAIN, DATED
  * and PROJECTION records, tag column optional); any other value kind is RH_ERR_UNSUPPORTED with a
- * message that names RH_KEY_STR.  Strings of 32 bytes or more stay with the encoded store
- * (rh_estore_*): a 64-byte row would need sort / search / merge instantiations of its own.       */
+ * message that names RH_KEY_STR.  Strings of 64 bytes or more stay with the encoded store
+ * (rh_estore_*).
+ * 64-byte rows and the one-launch kernels: the store's small questions (rh_store_ranks / _select /
+ * _keys of at most 64 entries, rh_store_aggregate_keys) and its protocol rounds of at most 16
+ * segments are served, for rows of at most 32 bytes, by kernels that carry the keys inline in
+ * their arguments.  A store of 64-byte rows sends them down the general device path instead (the
+ * one RSOS_HIP_QUERY_FUSED=0 / RSOS_HIP_ROUND_FUSED=0 select for any store): the answers are the
+ * same on either route, and nothing changes for rows of at most 32 bytes.                        */
 typedef enum rh_key_kind {
     RH_KEY_UNIT = 0,
     RH_KEY_U32 = 1,
@@ -166,7 +175,7 @@ int         rh_abi_version(void);
 const char *rh_last_error(void);
 /* 1 if a specialised kernel exists for this schema, 0 if it needs the encoded path, <0 bad.
  * VARBYTES values: 1 with unit, u32, u64, 16- and 32-byte keys, 0 with any other key length.
- * STR keys: 1 for (STR, 16 | 32, VARBYTES); RH_ERR_ARG for STR with any other key_len; 0 for
+ * STR keys: 1 for (STR, 16 | 32 | 64, VARBYTES); RH_ERR_ARG for STR with any other key_len; 0 for
  * STR with any other value kind.                                                               */
 int         rh_schema_supported(const rh_schema *schema);
 /* canonical-encoding length of a present / tombstone record of this schema (host helper).

@@ -20,7 +20,7 @@ bool schema_instantiated(int kk, int kl, int vk, int vl);
 bool var_key_supported(int kk, int kl);
 hipError_t launch_lift_var(int kk, int kl, int rk, bool tags, const VarCols &c, uint64_t n, uint8_t *fps,
                            uint8_t *bsums, hipStream_t st, bool *supported);
-// Short string keys in rows of width w (lift_str.hpp) with variable-length values: w 16 or 32;
+// Short string keys in rows of width w (lift_str.hpp) with variable-length values: w 16, 32 or 64;
 // *supported = false for any other width
 bool str_key_supported(int w);
 hipError_t launch_lift_str(int w, int rk, bool tags, const VarCols &c, uint64_t n, uint8_t *fps, uint8_t *bsums,

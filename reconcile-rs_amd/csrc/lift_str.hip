@@ -1,4 +1,4 @@
-// lift_str.hip -- the short-string-key lift (lift_str.hpp) instantiated for the two row widths, and
+// lift_str.hip -- the short-string-key lift (lift_str.hpp) instantiated for the three row widths, and
 // its launcher.
 #include "internal.hpp"
 #include "lift_str.hpp"
@@ -34,14 +34,15 @@ hipError_t launch_str_width(int rk, bool tags, const VarCols &c, uint64_t n, uin
 
 }  // namespace
 
-bool str_key_supported(int w) { return w == 16 || w == 32; }
+bool str_key_supported(int w) { return w == 16 || w == 32 || w == 64; }
 
 hipError_t launch_lift_str(int w, int rk, bool tags, const VarCols &c, uint64_t n, uint8_t *fps, uint8_t *bsums,
                            hipStream_t st, bool *supported) {
     *supported = str_key_supported(w);
     if (!*supported || n == 0) return hipSuccess;
-    return w == 16 ? launch_str_width<16>(rk, tags, c, n, fps, bsums, st)
-                   : launch_str_width<32>(rk, tags, c, n, fps, bsums, st);
+    return w == 16   ? launch_str_width<16>(rk, tags, c, n, fps, bsums, st)
+           : w == 32 ? launch_str_width<32>(rk, tags, c, n, fps, bsums, st)
+                     : launch_str_width<64>(rk, tags, c, n, fps, bsums, st);
 }
 
 }  // namespace rh

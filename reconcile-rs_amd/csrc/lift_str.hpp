@@ -1,5 +1,5 @@
 // lift_str.hpp -- the lift of records whose key is a short string held in a fixed-width row
-// (RH_KEY_STR: String / Vec<u8> / &str of at most W - 1 bytes, W = 16 or 32) and whose value is a
+// (RH_KEY_STR: String / Vec<u8> / &str of at most W - 1 bytes, W = 16, 32 or 64) and whose value is a
 // run of bytes of per-record length (RH_VAL_VARBYTES).  The key row is the string's L bytes, zero
 // bytes up to offset W - 2, and L in byte W - 1 (include/rsos_hip.h): to every sort, search and
 // merge it is a RH_KEY_BYTES row of width W; only this lift knows that the *string* is hashed --
@@ -8,15 +8,25 @@
 // The message of a present record:
 //   u64 L | L key bytes | DATED: phys u64, logical u32, node u64 | DATED/PROJECTION: u32 variant |
 //   u64 vlen | value bytes
-// and a tombstone's ends after the variant word (12..63 bytes: one block).  The prefix is
-// P = 8 + L + TL bytes (TL = stamp + variant + 8: 8, 12 or 32), 16..71, in general no multiple
-// of 4: everything behind the key starts at a per-record byte offset.  So the fields behind the
+// and a tombstone's ends after the variant word (12..63 bytes, one block, for W <= 32; up to 95
+// bytes, two blocks, for W = 64).  The prefix is P = 8 + L + TL bytes (TL = stamp + variant + 8: 8,
+// 12 or 32), 16..71 for W <= 32 and up to 103 for W = 64, in general no multiple of 4: everything
+// behind the key starts at a per-record byte offset.  So the fields behind the
 // key -- the TL/4 tail words, and the value words of the block in which the prefix ends -- are one
-// stream of words that is moved up by L bytes in registers: (L & 3) bytes with a funnel shift,
-// (L >> 2) words with a select per bit of it, every register index a compile-time constant.  The
+// stream of words that is moved up by L bytes: (L & 3) bytes with a funnel shift, (L >> 2) words
+// with a select per bit of it in registers (W <= 32) or through LDS (W = 64, below), every
+// register index a compile-time constant.  The
 // value's bytes of that block are loaded from the value's start (never from an address below it)
 // and take part in the same shift; every later block is value bytes alone, from
 // vstart + boff - P >= vstart.
+//
+// W = 64: the key itself can end in block 1 (8 + L > 64 from L = 57), and the tail words and the
+// first value words can lie on either side of the block edge.  Both prefix blocks are windows of
+// the same stream: message word K is stream word K - 2 - (L >> 2), moved up by (L & 3) bytes.
+// Here the word offset is taken through LDS (compose64): each lane writes its stream to a column
+// of its own and reads 17 words back from a run-time slot -- select passes for 16 word offsets
+// over two blocks measured x1.30-1.34 of the encoded route, this form x1.21-1.26 (DESIGN.md
+// section 6).  Still no scratch and no register indexed at run time.
 //
 // Read per record: the W-byte row + stamp + tag + one 8 B offset + the value bytes; written: 32 B.
 //
@@ -35,13 +45,13 @@ constexpr int STR_PER_WAVE = 64 * 4;
 
 template <int W, int RK>
 struct StrReader {
-    static_assert(W == 16 || W == 32, "a key row is 16 or 32 bytes");
+    static_assert(W == 16 || W == 32 || W == 64, "a key row is 16, 32 or 64 bytes");
     static constexpr int STAMP = RK == REC_DATED ? 20 : 0, TAG = RK == REC_PLAIN ? 0 : 4;
     static constexpr int TL = STAMP + TAG + 8, TLW = TL / 4;  // the fields behind the key, up to the value's length
     static constexpr int KW = W / 4;                          // words of a key row
     static constexpr int PMAX = 8 + (W - 1) + TL;             // the longest prefix
     static constexpr int QBITS = W == 32 ? 3 : 2;             // L >> 2 is below 1 << QBITS
-    static_assert(PMAX <= 71, "the prefix ends in block 0 or 1");
+    static_assert(W == 64 ? PMAX <= 103 : PMAX <= 71, "the prefix ends in block 0 or 1");
 
     VarCols c;            // keys, stamps, tags, voffs and dst rebased to row `base`; values the whole heap
     uint64_t base;
@@ -93,6 +103,12 @@ struct StrReader {
         ldw<KW, 16>(c.keys + t * (uint32_t)W, h.kw);  // the whole row, W-byte aligned
         if constexpr (RK == REC_DATED) load_stamp<uint32_t>(c, t, h.sw);
     }
+    // W = 64, block 1: the row's last two words (the key bytes from offset 56) and the stamp
+    __device__ __forceinline__ void load_head_hi(Head &h) const {
+        static_assert(W == 64, "only a 64-byte row reaches block 1");
+        ldw<2, 8>(c.keys + t * (uint32_t)W + 56u, h.kw + 14);
+        if constexpr (RK == REC_DATED) load_stamp<uint32_t>(c, t, h.sw);
+    }
 
     // The fields behind the key as words: stamp, State variant, the value's u64 length
     __device__ __forceinline__ void tail_words(const Head &h, uint32_t tw[TLW]) const {
@@ -117,6 +133,7 @@ struct StrReader {
     // bytes by a funnel shift, (L >> 2) words by one select pass per bit of it.  Bytes of the row
     // at and past L (padding, the length byte) are masked to zero before they enter the message.
     __device__ __forceinline__ void compose(const Head &h, const uint32_t v[16], uint32_t m[16]) const {
+        static_assert(W != 64, "a 64-byte row's prefix blocks: compose64");
         constexpr int NST = 14;  // stream words that can reach block 0: its word 0 is message word 2 at least
         uint32_t st[NST];
         uint32_t tw[TLW];
@@ -149,10 +166,59 @@ struct StrReader {
         for (int j = 0; j < 16; j++) m[j] = e[j];
     }
 
+    // W = 64, both prefix blocks at once, the word shift through LDS.  The lane writes its stream
+    // (tail words, 16 value words) to a column of its own -- slot s of lane t at word 256 s + t, so
+    // whatever slots a wave's lanes address, each lane stays in its own bank -- and reads back the 17
+    // words t[k] = stream[base + k], base = 16 blk - 3 - (L >> 2): a run-time word offset with no
+    // select pass and no register indexed at run time.  Indices below 0 (the key's place, and
+    // words 0 and 1 of block 0) read slot 0, which holds zero.  The highest index is 13 in block 0
+    // and 29 - (L >> 2) in block 1, where P > 64 means L >= 57 - TL: at most TLW + 15, the last
+    // stream word (dated 23, projection 18, plain 17); it is clamped all the same.  A lane reads only what
+    // it wrote itself, in program order: no barrier.  Then the byte shift and the key mask as in
+    // compose: message word 2 + j holds key word j, so block 0 takes words 0..13 and block 1 words
+    // 14 and 15 (word 15's last byte, the length, is always at or past L).  A tombstone's stream is
+    // zero behind its variant word, so its blocks are zero past its last byte.  A wave whose lanes
+    // are at block 0 and at block 1 runs this once.
+    __device__ __forceinline__ void compose64(bool hi, const Head &h, const uint32_t v[16], uint32_t m[16]) const {
+        static_assert(W == 64, "the LDS composition is the 64-byte row's");
+        constexpr int NSTR = TLW + 16;
+        __shared__ uint32_t lds[(NSTR + 1) * 256];  // (both kernels launch 256 lanes a workgroup)
+        uint32_t *col = lds + threadIdx.x;
+        uint32_t tw[TLW];
+        tail_words(h, tw);
+        col[0] = 0u;
+#pragma unroll
+        for (int i = 0; i < TLW; i++) col[(1 + i) * 256] = tw[i];
+#pragma unroll
+        for (int i = 0; i < 16; i++) col[(1 + TLW + i) * 256] = v[i];
+        const uint32_t s8 = (klen & 3u) * 8u, q = klen >> 2;
+        const int base = (hi ? 13 : -3) - (int)q;
+        uint32_t t[17];
+#pragma unroll
+        for (int k = 0; k < 17; k++) {
+            int i = base + k;
+            i = i < -1 ? -1 : i;
+            i = i > NSTR - 1 ? NSTR - 1 : i;
+            t[k] = col[(i + 1) * 256];
+        }
+#pragma unroll
+        for (int k = 0; k < 16; k++) m[k] = up_bytes(t[k + 1], t[k], s8);
+        const uint32_t bm = (1u << s8) - 1u;
+        if (hi) {
+#pragma unroll
+            for (int j = 14; j < 16; j++) m[j - 14] |= (uint32_t)j < q ? h.kw[j] : ((uint32_t)j == q ? (h.kw[j] & bm) : 0u);
+        } else {
+            m[0] = klen;
+#pragma unroll
+            for (int j = 0; j < 14; j++) m[2 + j] |= (uint32_t)j < q ? h.kw[j] : ((uint32_t)j == q ? (h.kw[j] & bm) : 0u);
+        }
+    }
+
     // Block 1 of a record whose prefix ends there (P = 65..71: W = 32, DATED, L = 25..31): the last
     // bytes of the value's length, then the value from its start.  Message word 16 + k is stream
     // word 14 + k - (L >> 2), and L >> 2 is 6 or 7 here: one select, then the byte shift.
     __device__ __forceinline__ void compose_hi(const uint32_t v[16], uint32_t m[16]) const {
+        static_assert(W != 64, "a 64-byte row's prefix blocks: compose64");
         static_assert(PMAX <= 64 || TLW == 8, "block 1 holds prefix bytes for W = 32 DATED alone");
         const uint32_t s8 = (klen & 3u) * 8u;
         const bool q7 = (klen >> 2) == 7u;
@@ -183,6 +249,9 @@ struct StrReader {
         const uint32_t vb = blen > pbytes ? blen - pbytes : 0u;  // (a tombstone: blen = p - 8, none)
         Head h;
         if (b0) load_head(h);
+        if constexpr (W == 64) {
+            if (b1) load_head_hi(h);
+        }
         uint32_t v[16];
         if (vb) {
             // partial: zero past the vb value bytes, so a composed block is zero past blen; a full
@@ -192,13 +261,22 @@ struct StrReader {
 #pragma unroll
             for (int j = 0; j < 16; j++) v[j] = 0u;
         }
-        if (b0) {
-            compose(h, v, m);
-        } else if (b1) {
-            if constexpr (PMAX > 64) compose_hi(v, m);
-        } else {
+        if constexpr (W == 64) {
+            if (b0 || b1) {
+                compose64(b1, h, v, m);
+            } else {
 #pragma unroll
-            for (int j = 0; j < 16; j++) m[j] = v[j];
+                for (int j = 0; j < 16; j++) m[j] = v[j];
+            }
+        } else {
+            if (b0) {
+                compose(h, v, m);
+            } else if (b1) {
+                if constexpr (PMAX > 64) compose_hi(v, m);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 16; j++) m[j] = v[j];
+            }
         }
     }
 

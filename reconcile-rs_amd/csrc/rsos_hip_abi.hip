@@ -191,8 +191,9 @@ int check_schema(const rh_schema *s) {
     if (s->reserved != 0) return fail(RH_ERR_ARG, "schema.reserved must be 0");
     if (s->key_kind == RH_KEY_U32 && s->key_len != 4) return fail(RH_ERR_ARG, "u32 key needs key_len 4");
     if (s->key_kind == RH_KEY_U64 && s->key_len != 8) return fail(RH_ERR_ARG, "u64 key needs key_len 8");
-    if (s->key_kind == RH_KEY_STR && s->key_len != 16 && s->key_len != 32)
-        return fail(RH_ERR_ARG, "RH_KEY_STR needs key_len 16 or 32 (the row width: strings of up to 15 or 31 bytes)");
+    if (s->key_kind == RH_KEY_STR && s->key_len != 16 && s->key_len != 32 && s->key_len != 64)
+        return fail(RH_ERR_ARG,
+                    "RH_KEY_STR needs key_len 16, 32 or 64 (the row width: strings of up to 15, 31 or 63 bytes)");
     if (s->value_kind == RH_VAL_U32 && s->value_len != 4) return fail(RH_ERR_ARG, "u32 value needs value_len 4");
     if (s->value_kind == RH_VAL_U64 && s->value_len != 8) return fail(RH_ERR_ARG, "u64 value needs value_len 8");
     if (s->value_kind == RH_VAL_VARBYTES && s->value_len != 0)
@@ -297,7 +298,7 @@ int lift_dispatch(const rh_schema &s, const rh_columns &c, size_t n, uint8_t *fp
         hipError_t ev = rh::launch_lift_str((int)s.key_len, s.record_kind, tags, dc, n, fps, bs, st, &supported);
         if (supported && ev == hipSuccess && dual)
             ev = rh::launch_lift_str((int)s.key_len, RH_REC_PROJECTION, tags, dc, n, fps2, bs2, st, &supported);
-        if (!supported) return fail(RH_ERR_UNSUPPORTED, "RH_KEY_STR rows are 16 or 32 bytes wide");
+        if (!supported) return fail(RH_ERR_UNSUPPORTED, "RH_KEY_STR rows are 16, 32 or 64 bytes wide");
         if (ev != hipSuccess) return fail(RH_ERR_HIP, std::string("lift launch: ") + hipGetErrorString(ev));
         return RH_OK;
     }
@@ -2926,8 +2927,8 @@ struct rh_store {
             out->size = size();
             return RH_OK;
         }
-        if (query_fused) {
-            uint8_t k2[64] = {0};
+        if (query_fused && tiny_kernels_serve()) {
+            uint8_t k2[2 * rh::ROUND_TINY_KL] = {0};
             if (lo_kind) memcpy(k2, lo_key, kl);
             if (hi_kind) memcpy(k2 + kl, hi_key, kl);
             return query_tiny(2, k2, 2 * kl, 1, lo_kind, hi_kind, out, sizeof(rh_aggregate));
@@ -2961,6 +2962,11 @@ struct rh_store {
     PinnedVec<uint8_t> qt_buf{hipHostMallocCoherent};
     uint64_t qt_seq = 0;
     int query_fused = getenv("RSOS_HIP_QUERY_FUSED") ? atoi(getenv("RSOS_HIP_QUERY_FUSED")) : 1;
+    // The one-launch kernels (k_query_tiny, k_round_tiny) carry their keys inline in the kernel's
+    // arguments, sized for rows of at most ROUND_TINY_KL = 32 bytes.  A store of 64-byte rows
+    // (RH_KEY_STR, key_len 64) takes the general device path for the small questions and for every
+    // round -- the one RSOS_HIP_QUERY_FUSED=0 / RSOS_HIP_ROUND_FUSED=0 select -- with the same answers.
+    bool tiny_kernels_serve() const { return kl <= rh::ROUND_TINY_KL; }
     int query_tiny(int mode, const void *in, size_t in_bytes, uint64_t m, int lo_kind, int hi_kind, void *out,
                    size_t out_bytes) {
         int rc;
@@ -2997,7 +3003,8 @@ struct rh_store {
     }
     int ranks(const void *keys, size_t m, uint64_t *out) {
         int rc;
-        if (query_fused && m <= rh::QUERY_TINY) return query_tiny(0, keys, m * kl, m, 0, 0, out, m * 8);
+        if (query_fused && tiny_kernels_serve() && m <= rh::QUERY_TINY)
+            return query_tiny(0, keys, m * kl, m, 0, 0, out, m * 8);
         if ((rc = q_keys.ensure(m * kl + 64)) || (rc = q_rank.ensure(m)) || (rc = q_drank.ensure(m)) ||
             (rc = q_merged.ensure(m)))
             return rc;
@@ -3251,7 +3258,7 @@ struct rh_store {
         uint64_t *hdr = reinterpret_cast<uint64_t *>(r_out.p);
         const int sq = policy == RH_POLICY_SQRT_FAN_OUT;
         uint64_t h[5];
-        if (zero_copy && round_fused && kl <= rh::ROUND_TINY_KL && r <= rh::ROUND_TINY_SEGS) {
+        if (zero_copy && round_fused && tiny_kernels_serve() && r <= rh::ROUND_TINY_SEGS) {
             // a tiny round whole in one launch (round_tiny.hpp): the bound keys' searches in both
             // runs, the bounds, decisions and emission, the per-segment arrays in LDS; the host
             // waits for the sequence word the kernel stores last into the mapped output
@@ -3596,7 +3603,7 @@ int rh_store_create(int device, const rh_schema *schema, rh_store **out) {
         return fail(RH_ERR_UNSUPPORTED, "store needs a schema with a specialised lift kernel");
     // string rows sort, search and merge as byte rows of their width
     rh::StoreKeyOps *kops = rh::store_key_ops(is_str(*schema) ? RH_KEY_BYTES : schema->key_kind, key_row(*schema));
-    if (!kops) return fail(RH_ERR_UNSUPPORTED, "store keys must be u32, u64 or 8/16/32-byte arrays");
+    if (!kops) return fail(RH_ERR_UNSUPPORTED, "store keys must be u32, u64 or 8/16/32-byte arrays (64-byte rows: RH_KEY_STR)");
     RH_HIP(hipSetDevice(device));
     rh_store *s = new rh_store();
     s->device = device;
@@ -3710,7 +3717,7 @@ int rh_store_keys(rh_store *s, uint64_t lo, uint64_t hi, void *host_out) {
         return RH_OK;
     }
     RH_HIP(hipSetDevice(s->device));
-    if (s->query_fused && hi - lo <= rh::QUERY_TINY) {  // select and short dumps: one launch
+    if (s->query_fused && s->tiny_kernels_serve() && hi - lo <= rh::QUERY_TINY) {  // select and short dumps: one launch
         uint64_t rk[rh::QUERY_TINY];
         for (uint64_t i = lo; i < hi; i++) rk[i - lo] = i;
         return s->query_tiny(1, rk, (hi - lo) * 8, hi - lo, 0, 0, host_out, (hi - lo) * s->kl);

@@ -1510,6 +1510,7 @@ hipError_t launch_merge_kernel(int kk, int kl, int payload, const uint8_t *akeys
                                                            st, heap, heap_base, tileU);                            \
     }
     RH_MK(KEY_U32, 4) RH_MK(KEY_U64, 8) RH_MK(KEY_BYTES, 8) RH_MK(KEY_BYTES, 16) RH_MK(KEY_BYTES, 32)
+    RH_MK(KEY_BYTES, 64)
 #undef RH_MK
     return hipErrorInvalidValue;
 }
@@ -1656,16 +1657,28 @@ struct KeyOps final : StoreKeyOps {
         return hipGetLastError();
     }
 
+    // The one-launch kernels hold their keys inline in the kernel's arguments, sized for rows of
+    // at most ROUND_TINY_KL bytes: a wider row (the 64-byte string rows) is not built for them, and
+    // the store sends its small questions and tiny rounds down the general device path
+    // (tiny_kernels_serve).
     hipError_t query_tiny(const QueryTiny &a, hipStream_t st) override {
-        if (a.m > QUERY_TINY || (a.mode == 2 && a.m != 1)) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((k_query_tiny<KK, KL>), dim3(1), dim3(1024), 0, st, a);
-        return hipGetLastError();
+        if constexpr (KL <= (int)ROUND_TINY_KL) {
+            if (a.m > QUERY_TINY || (a.mode == 2 && a.m != 1)) return hipErrorInvalidValue;
+            hipLaunchKernelGGL((k_query_tiny<KK, KL>), dim3(1), dim3(1024), 0, st, a);
+            return hipGetLastError();
+        } else {
+            return hipErrorInvalidValue;
+        }
     }
 
     hipError_t round_tiny(const RoundTiny &a, hipStream_t st) override {
-        if (a.r == 0 || a.r > ROUND_TINY) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((k_round_tiny<KK, KL>), dim3(1), dim3(ROUND_TINY_THREADS), 0, st, a);
-        return hipGetLastError();
+        if constexpr (KL <= (int)ROUND_TINY_KL) {
+            if (a.r == 0 || a.r > ROUND_TINY) return hipErrorInvalidValue;
+            hipLaunchKernelGGL((k_round_tiny<KK, KL>), dim3(1), dim3(ROUND_TINY_THREADS), 0, st, a);
+            return hipGetLastError();
+        } else {
+            return hipErrorInvalidValue;
+        }
     }
 
     int compare_keys_host(const uint8_t *a, const uint8_t *b) const override {
@@ -1689,6 +1702,8 @@ StoreKeyOps *store_key_ops(int kk, int kl) {
     static KeyOps<KEY_BYTES, 16> b16;
     static KeyOps<KEY_BYTES, 32> b32;
     static KeyOps<KEY_BYTES, 8> b8;
+    static KeyOps<KEY_BYTES, 64> b64;  // the 64-byte string rows (RH_KEY_STR); no lift of plain 64-byte keys
+    if (kk == KEY_BYTES && kl == 64) return &b64;
     if (kk == KEY_U32 && kl == 4) return &u32;
     if (kk == KEY_U64 && kl == 8) return &u64;
     if (kk == KEY_BYTES && kl == 16) return &b16;

@@ -138,10 +138,10 @@ int key_codec(const rh_schema *s, int form, KeyCodec *kc) {
     if (s->key_kind == RH_KEY_U32 && s->key_len == 4 && form == RH_FORM_ARRAY) *kc = {RH_KEY_U32, form, 4};
     else if (s->key_kind == RH_KEY_U64 && s->key_len == 8 && form == RH_FORM_ARRAY) *kc = {RH_KEY_U64, form, 8};
     else if (s->key_kind == RH_KEY_BYTES && s->key_len > 0) *kc = {RH_KEY_BYTES, form, s->key_len};
-    else if (s->key_kind == RH_KEY_STR && (s->key_len == 16 || s->key_len == 32) && form == RH_FORM_VEC)
+    else if (s->key_kind == RH_KEY_STR && (s->key_len == 16 || s->key_len == 32 || s->key_len == 64) && form == RH_FORM_VEC)
         *kc = {RH_KEY_STR, form, s->key_len};
     else if (s->key_kind == RH_KEY_STR)
-        return rh::set_error(RH_ERR_ARG, "RH_KEY_STR wire keys are Vec<u8> / String: RH_FORM_VEC, key_len 16 or 32");
+        return rh::set_error(RH_ERR_ARG, "RH_KEY_STR wire keys are Vec<u8> / String: RH_FORM_VEC, key_len 16, 32 or 64");
     else return rh::set_error(RH_ERR_ARG, "wire keys must be u32, u64 or byte strings (RH_FORM_VEC only for bytes)");
     return RH_OK;
 }

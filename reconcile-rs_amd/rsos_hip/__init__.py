@@ -11,6 +11,9 @@ behaviour), so callers and tests read like the reference's own:
                        which rbsr consumes as RsosView<K> (rbsr/src/rsos_view.rs:55-91)
   FingerprintMap       the same with the host owning K and V and single-record updates staged
                        into one device batch (the Rust binding's HipFingerprintMap)
+  pack_str_keys        String / Vec<u8> keys of at most 15 / 31 / 63 bytes as the 16- / 32- / 64-byte
+                       rows of a 'str15' / 'str31' / 'str63' schema (RH_KEY_STR); the store and
+                       FingerprintMap take such keys as str or bytes
 
 All hashing runs in the HIP kernels of librsos_hip.so; nothing here computes a
 fingerprint on the CPU.  torch is used only for device memory and streams.

@@ -25,7 +25,8 @@ class RecordSchema:
     def plain(key: str, value: str) -> "RecordSchema":
         """FingerprintTreeMap<K, V>: lift(k, v).  key/value: 'u32', 'u64', 'bytesN'; value 'var':
         Vec<u8> / String of a length that differs per record (a heap and offsets, VAL_VARBYTES);
-        key 'str15' / 'str31': String / Vec<u8> of at most 15 / 31 bytes in a 16- / 32-byte row
+        key 'str15' / 'str31' / 'str63': String / Vec<u8> of at most 15 / 31 / 63 bytes in a 16- / 32- /
+        64-byte row
         (KEY_STR, strkeys.pack_str_keys), with 'var' values."""
         kk, kl = _kind(key, True)
         vk, vl = _kind(value, False)
@@ -94,9 +95,9 @@ def _kind(name: str, key: bool):
         if key:
             raise ValueError("keys are fixed-width: 'var' is a value kind")
         return A.VAL_VARBYTES, 0
-    if name in ("str15", "str31"):  # named by the longest string; the row is one byte wider
+    if name in ("str15", "str31", "str63"):  # named by the longest string; the row is one byte wider
         if not key:
-            raise ValueError("'str15' / 'str31' are key kinds: a string value is 'var'")
+            raise ValueError("'str15' / 'str31' / 'str63' are key kinds: a string value is 'var'")
         return A.KEY_STR, int(name[3:]) + 1
     if name.startswith("bytes"):
         return (A.KEY_BYTES if key else A.VAL_BYTES), int(name[5:])

@@ -13,7 +13,7 @@ Keys and fingerprints are held in rank order in HBM with the block / super-block
 select and range bounds are answered on the device.  Record payloads are lifted on ingest and
 not kept on the device (the caller owns K and V, as the reference's map does).  Keys are
 fixed-width: bytes of schema.key_len for byte keys (memcmp order = Ord of [u8; L]), ints for
-u32/u64 keys; 'str15' / 'str31' keys are given as str (UTF-8) or bytes and come back as bytes
+u32/u64 keys; 'str15' / 'str31' / 'str63' keys are given as str (UTF-8) or bytes and come back as bytes
 (strkeys.py: the padded rows' memcmp order = Ord of String).
 """
 from __future__ import annotations

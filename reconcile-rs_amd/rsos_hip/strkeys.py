@@ -20,8 +20,8 @@ def _raw(k: StrKey) -> bytes:
 
 def pack_str_keys(keys: Iterable[StrKey], width: int) -> np.ndarray:
     """The (n, width) uint8 rows of `keys` (str: its UTF-8).  ValueError past width - 1 bytes."""
-    if width not in (16, 32):
-        raise ValueError("a string key row is 16 or 32 bytes wide")
+    if width not in (16, 32, 64):
+        raise ValueError("a string key row is 16, 32 or 64 bytes wide")
     raws = [_raw(k) for k in keys]
     rows = np.zeros((len(raws), width), np.uint8)
     for i, b in enumerate(raws):

@@ -24,11 +24,12 @@
 //! fails loudly on those (`lift` panics on an encoder failure, fingerprint.rs:240-246), so
 //! this crate panics with the library's message.
 //!
-//! String keys: `HipFingerprintMap<ShortString<32>, String>` (or `ShortString<16>`, and
-//! `Entry<Timestamp, String>` / `State<String>` values) is the column-store map of a reference
-//! `FingerprintTreeMap<String, String>` whose keys are at most 31 (15) bytes: same fingerprints,
+//! String keys: `HipFingerprintMap<ShortString<64>, String>` (or `ShortString<32>` /
+//! `ShortString<16>`, and `Entry<Timestamp, String>` / `State<String>` values) is the column-store
+//! map of a reference `FingerprintTreeMap<String, String>` whose keys are at most 63 (31, 15)
+//! bytes -- Kubernetes object names fit the 64-byte row: same fingerprints,
 //! same order (`strkey.rs`, `RH_KEY_STR`), with rounds, staged inserts and the host tier as for any
-//! fixed-width key.  Keys of 32 bytes or more take [`HipEncodedMap`].
+//! fixed-width key.  Keys of 64 bytes or more take [`HipEncodedMap`].
 
 mod encoded;
 mod ffi;

@@ -13,7 +13,7 @@ use serde::{Deserialize, Deserializer, Serialize, Serializer};
 
 use crate::{ffi, GpuKey};
 
-/// A byte string of at most `W - 1` bytes, `W` = 16 or 32.  `Ord` is the bytes' (that of
+/// A byte string of at most `W - 1` bytes, `W` = 16, 32 or 64.  `Ord` is the bytes' (that of
 /// `Vec<u8>` / `String`), and agrees with the `memcmp` order of [`ShortString::pack`]'s rows.  It
 /// serialises exactly as a `Vec<u8>` of the same bytes -- for rsos's canonical encoder and for
 /// bincode the bytes a `String` of that content gives too.
@@ -99,7 +99,7 @@ macro_rules! short_string_key {
         }
     )*};
 }
-short_string_key!(16 32);
+short_string_key!(16 32 64);
 
 #[cfg(test)]
 mod tests {
@@ -116,5 +116,28 @@ mod tests {
         assert!(keys.iter().all(|k| ShortString::<32>::unpack(&k.pack()).as_ref() == Some(k)));
         assert!(ShortString::<32>::new(vec![0u8; 32]).is_none());
         assert!(ShortString::<16>::try_from("exactly 16 bytes").is_err());
+    }
+
+    #[test]
+    fn row_order_is_string_order_at_64() {
+        let long = [b'k'; 63];
+        let mut other = long;
+        other[62] = b'l';
+        let zeros = [0u8; 63];
+        let strs: Vec<&[u8]> = vec![
+            b"", b"\0", b"\0\0", &zeros[..62], &zeros, b"a", b"a\0", b"a\x01", b"ab", &long[..62], &long, &other,
+            &[0xff; 62], &[0xff; 63], b"namespace/ReplicaSet/frontend-web-7c9d8b6f54-x7k2p",
+        ];
+        let mut keys: Vec<ShortString<64>> = strs.iter().map(|s| ShortString::new(*s).unwrap()).collect();
+        let mut rows: Vec<[u8; 64]> = keys.iter().map(|k| k.pack()).collect();
+        keys.sort();
+        rows.sort();
+        assert_eq!(rows, keys.iter().map(|k| k.pack()).collect::<Vec<_>>());
+        assert!(keys.iter().all(|k| ShortString::<64>::unpack(&k.pack()).as_ref() == Some(k)));
+        assert_eq!(ShortString::<64>::MAX, 63);
+        assert!(ShortString::<64>::new(vec![0u8; 64]).is_none());
+        let mut bad = ShortString::<64>::new(&b"abc"[..]).unwrap().pack();
+        bad[63] = 64;
+        assert!(ShortString::<64>::unpack(&bad).is_none());
     }
 }

@@ -2,18 +2,20 @@
 without it: rh_lift_encoded_async over the same records' canonical bytes, already resident (the
 host's encoding work is left out, which favours the baseline).
 
-10 M seeded records, str31 keys, dated, a tag column (all present), value lengths uniform in
-[0, 256), two key-length mixes:
-  uniform  key lengths uniform in 0..31
-  full     every key 31 bytes
+10 M seeded records, str31 keys (--width 32; 16, 32 and 64 are the row widths, several may be
+given), dated, a tag column (all present), value lengths uniform in [0, 256), two key-length mixes:
+  uniform  key lengths uniform in 0..W-1
+  full     every key W-1 bytes
 Per mix the two routes alternate in one process, each launch between two device events, `--reps`
 launches each after a warm-up; the two outputs are compared before anything is timed.  One JSON
 line per mix goes to --out:
-  bytes moved by the byte model (str: the 32 B row + stamp + tag + one 8 B offset + the value bytes
+  bytes moved by the byte model (str: the W-byte row + stamp + tag + one 8 B offset + the value bytes
   in, 32 B out, per record; encoded: the canonical bytes + one 8 B offset in, 32 B out), GiB/s and
   records/s of both routes (medians), their ratio, and the baseline's spread over its alternated
   repetitions: (p90 - p10) / median of its launch times.
 Criterion: str median <= encoded median * (1 + spread).
+With --width 32,64 in one run, each width-64 line also carries the str63 target: its ratio to the
+encoded route at most the str31 ratio of the same mix and run, times (1 + the encoded route's spread).
 
 Kernel times: a separate run under `rocprofv3 --kernel-trace --stats -- python scripts/str_lift_probe.py`.
 """
@@ -28,12 +30,11 @@ sys.path.insert(0, os.environ.get("RSOS_HIP_TREE") or
 import torch  # noqa: E402
 from rsos_hip import RecordSchema, lift_encoded, lift_records  # noqa: E402
 
-W = 32
 TAIL = 20 + 4 + 8  # stamp, State variant, the value's u64 length
 
 
-def key_rows(mix, n, g):
-    """n rows in RH_KEY_STR form: L bytes, zero padding, L in byte 31."""
+def key_rows(mix, n, g, W):
+    """n rows in RH_KEY_STR form: L bytes, zero padding, L in byte W - 1."""
     if mix == "uniform":
         klen = torch.randint(0, W, (n,), dtype=torch.int64, device="cuda", generator=g)
     else:
@@ -44,7 +45,7 @@ def key_rows(mix, n, g):
     return rows, klen
 
 
-def canonical_bytes(cols, klen, lens, voffs, chunk=1 << 19):
+def canonical_bytes(cols, klen, lens, voffs, W, chunk=1 << 19):
     """The records' canonical encodings, packed: u64 L, the L key bytes, stamp, variant 0, u64
     value length, the value."""
     n = lens.numel()
@@ -94,20 +95,25 @@ def main():
     ap.add_argument("--records", type=int, default=10_000_000)
     ap.add_argument("--reps", type=int, default=24)
     ap.add_argument("--mixes", default="uniform,full")
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles",
-                                                  "str_lift_probe.jsonl"))
+    ap.add_argument("--width", default="32", help="row widths, comma separated (16, 32, 64)")
+    ap.add_argument("--out", default=None, help="default: profiles/str_lift_probe.jsonl; with a width of 64, "
+                                                "profiles/str63_lift_probe.jsonl")
     args = ap.parse_args()
     n = args.records
-    schema = RecordSchema.dated("str31", "var")
+    widths = [int(w) for w in args.width.split(",")]
+    if args.out is None:
+        args.out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles",
+                                "str63_lift_probe.jsonl" if 64 in widths else "str_lift_probe.jsonl")
     g = torch.Generator(device="cuda")
     lines = []
-    for mix in args.mixes.split(","):
+    for W, mix in ((w, m) for w in widths for m in args.mixes.split(",")):
+        schema = RecordSchema.dated(f"str{W - 1}", "var")
         g.manual_seed(200 + len(mix))
         lens = torch.randint(0, 256, (n,), dtype=torch.int64, device="cuda", generator=g)
         voffs = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
         voffs[1:] = torch.cumsum(lens, 0)
         total_v = int(voffs[-1])
-        rows, klen = key_rows(mix, n, g)
+        rows, klen = key_rows(mix, n, g, W)
         cols = {"keys": rows,
                 "phys": torch.randint(0, 1 << 62, (n,), dtype=torch.int64, device="cuda", generator=g),
                 "logical": torch.randint(0, 1 << 31, (n,), dtype=torch.int32, device="cuda", generator=g),
@@ -115,7 +121,7 @@ def main():
                 "tags": torch.zeros(n, dtype=torch.uint8, device="cuda"),
                 "values": torch.randint(0, 256, ((total_v + 3) // 4 * 4,), dtype=torch.uint8, device="cuda", generator=g),
                 "value_offsets": voffs}
-        enc, eoffs = canonical_bytes(cols, klen, lens, voffs)
+        enc, eoffs = canonical_bytes(cols, klen, lens, voffs, W)
         total_k = int(klen.sum())
         fps_s = torch.empty((n, 32), dtype=torch.uint8, device="cuda")
         bs_s = torch.empty(((n + 255) // 256, 32), dtype=torch.uint8, device="cuda")
@@ -141,7 +147,7 @@ def main():
         st = {k: stats([a.elapsed_time(b) for a, b in v]) for k, v in ev.items()}
         moved = {"str": n * (W + 20 + 1 + 8 + 32) + total_v,
                  "encoded": n * (8 + TAIL + 8 + 32) + total_k + total_v}
-        line = {"probe": "str_lift", "mix": mix, "records": n, "key_bytes": total_k, "value_bytes": total_v,
+        line = {"probe": "str_lift", "width": W, "mix": mix, "records": n, "key_bytes": total_k, "value_bytes": total_v,
                 "reps": args.reps}
         for k in routes:
             t = st[k]["median_ms"] / 1e3
@@ -151,6 +157,11 @@ def main():
         line["encoded_spread"] = spread
         line["str_over_encoded"] = st["str"]["median_ms"] / base["median_ms"]
         line["str_within_spread"] = st["str"]["median_ms"] <= base["median_ms"] * (1 + spread)
+        ref = [x for x in lines if x["width"] == 32 and x["mix"] == mix]
+        if W == 64 and ref:  # the str63 target, against the str31 ratio of this run
+            line["str31_over_encoded"] = ref[0]["str_over_encoded"]
+            line["target_ratio"] = ref[0]["str_over_encoded"] * (1 + spread)
+            line["meets_target"] = line["str_over_encoded"] <= line["target_ratio"]
         print(json.dumps(line), flush=True)
         lines.append(line)
         del cols, enc, eoffs, fps_s, bs_s, rows
