@@ -83,10 +83,22 @@ typedef enum rh_status {
  * one is ordered as its bytes say.  In a DEVICE key column, nonzero padding or a length byte above
  * W - 1 is a caller error that gives a wrong fingerprint, never an out-of-range access (the lift
  * clips the length and masks the padding).
- * Values under STR keys: RH_VAL_VARBYTES only (String -> String, String -> Vec<u8>; PLAIN, DATED
- * and PROJECTION records, tag column optional); any other value kind is RH_ERR_UNSUPPORTED with a
- * message that names RH_KEY_STR.  Strings of 64 bytes or more stay with the encoded store
- * (rh_estore_*).
+ * Values under STR keys: RH_VAL_VARBYTES (String -> String, String -> Vec<u8>) and the fixed-width
+ * kinds RH_VAL_UNIT, RH_VAL_U32 and RH_VAL_U64 (ReplicatedSet<String>, FingerprintTreeMap<String,
+ * u32>, String -> u64); PLAIN, DATED and PROJECTION records, tag column optional.  RH_VAL_BYTES is
+ * RH_ERR_UNSUPPORTED with a message that names RH_KEY_STR: a [u8; N] or Vec<u8> value under a
+ * string key is VARBYTES with equal lengths, bit for bit.  Strings of 64 bytes or more stay with
+ * the encoded store (rh_estore_*).
+ * (STR, UNIT | U32 | U64) is accepted by rh_lift_records_async, rh_lift_dual_async (two passes),
+ * rh_lift_host (host key rows validated first), rh_store_create / _load / _load_device / _apply /
+ * _apply_device / _apply_device_many / _stage and rh_sstore_create (each shard lifts strings; a
+ * host batch's key rows are validated for the whole batch before any shard changes).  Batches of a
+ * STR store of any size take the large-batch route with separate lift and search launches: the
+ * fused lift + search kernel and the small-batch kernel hash the row, not the string, and are not
+ * built for strings (rh_store_batch_stats: small_batches stays 0).  Not supported
+ * (RH_ERR_UNSUPPORTED, the message names RH_KEY_STR): rh_store_load_snapshot into such a store and
+ * rh_snapshot_decode_device with a STR schema -- a file's String / Vec keys have per-entry
+ * lengths, which the fixed-stride locate cannot walk.
  * 64-byte rows and the one-launch kernels: the store's small questions (rh_store_ranks / _select /
  * _keys of at most 64 entries, rh_store_aggregate_keys) and its protocol rounds of at most 16
  * segments are served, for rows of at most 32 bytes, by kernels that carry the keys inline in
@@ -100,7 +112,7 @@ typedef enum rh_key_kind {
     RH_KEY_BYTES = 3,
     RH_KEY_STR = 4
 } rh_key_kind;
-/* Value encodings: UNIT / U32 / U64 as the keys'; BYTES: a byte string of one length per map (value_len),
+/* Value encodings: UNIT / U32 / U64 as the keys' (under every key kind, RH_KEY_STR included); BYTES: a byte string of one length per map (value_len),
  * u64 LE length then the bytes; VARBYTES: Vec<u8> / String / &str of a length that differs per
  * record -- u64 LE length, then the bytes (:105-113) -- given as a heap and offsets (rh_var_values
  * below).  schema.value_len must be 0 for VARBYTES (RH_ERR_ARG otherwise).                      */
@@ -175,14 +187,15 @@ int         rh_abi_version(void);
 const char *rh_last_error(void);
 /* 1 if a specialised kernel exists for this schema, 0 if it needs the encoded path, <0 bad.
  * VARBYTES values: 1 with unit, u32, u64, 16- and 32-byte keys, 0 with any other key length.
- * STR keys: 1 for (STR, 16 | 32 | 64, VARBYTES); RH_ERR_ARG for STR with any other key_len; 0 for
- * STR with any other value kind.                                                               */
+ * STR keys: 1 for (STR, 16 | 32 | 64, UNIT | U32 | U64 | VARBYTES); RH_ERR_ARG for STR with any
+ * other key_len; 0 for (STR, *, BYTES, *).                                                      */
 int         rh_schema_supported(const rh_schema *schema);
 /* canonical-encoding length of a present / tombstone record of this schema (host helper).
  * VARBYTES values: the length of a present record with an EMPTY value -- the prefix the value's
  * bytes follow (key, stamp, State variant, the value's u64 length); the tombstone length as ever.
  * STR keys: both lengths are those of the EMPTY key (its u64 length alone) -- 8 + stamp + variant
- * + 8 for a present record with an empty value; add L for a key of L bytes.                     */
+ * + 8 for a present VARBYTES record with an empty value, 8 + stamp + variant + 0 / 4 / 8 for a
+ * unit / u32 / u64 value; add L for a key of L bytes.                                           */
 int64_t     rh_schema_record_len(const rh_schema *schema, int tombstone);
 
 /* ---- device-resident batch API (all pointers are device pointers) -------------------- */

@@ -26,6 +26,11 @@ bool str_key_supported(int w);
 hipError_t launch_lift_str(int w, int rk, bool tags, const VarCols &c, uint64_t n, uint8_t *fps, uint8_t *bsums,
                            hipStream_t st, bool *supported);
 
+// Short string keys with fixed-width values (lift_strfix.hpp): w 16, 32 or 64, value_kind unit, u32 or
+// u64; *supported = false for anything else.  One launch per lift
+hipError_t launch_lift_str_fixed(int w, int value_kind, int rk, bool tags, const DevCols &c, uint64_t n, uint8_t *fps,
+                                 uint8_t *bsums, hipStream_t st, bool *supported);
+
 hipError_t launch_lift_encoded(const uint8_t *bytes, const uint64_t *offs, uint64_t n, uint64_t limit,
                                uint8_t *fps, uint8_t *bsums, hipStream_t st);
 // fixed-length records: record i = bytes[i * len, (i + 1) * len), read limit `limit`

@@ -179,9 +179,12 @@ struct StrReader {
     // 14 and 15 (word 15's last byte, the length, is always at or past L).  A tombstone's stream is
     // zero behind its variant word, so its blocks are zero past its last byte.  A wave whose lanes
     // are at block 0 and at block 1 runs this once.
-    __device__ __forceinline__ void compose64(bool hi, const Head &h, const uint32_t v[16], uint32_t m[16]) const {
+    // NV: the value words behind the tail (16 here; lift_strfix.hpp's stream ends with the tail words,
+    // NV = 0, and whatever a block holds past them is read from slot 0 as zero).
+    template <int NV = 16>
+    __device__ __forceinline__ void compose64(bool hi, const Head &h, const uint32_t *v, uint32_t m[16]) const {
         static_assert(W == 64, "the LDS composition is the 64-byte row's");
-        constexpr int NSTR = TLW + 16;
+        constexpr int NSTR = TLW + NV;
         __shared__ uint32_t lds[(NSTR + 1) * 256];  // (both kernels launch 256 lanes a workgroup)
         uint32_t *col = lds + threadIdx.x;
         uint32_t tw[TLW];
@@ -190,7 +193,7 @@ struct StrReader {
 #pragma unroll
         for (int i = 0; i < TLW; i++) col[(1 + i) * 256] = tw[i];
 #pragma unroll
-        for (int i = 0; i < 16; i++) col[(1 + TLW + i) * 256] = v[i];
+        for (int i = 0; i < NV; i++) col[(1 + TLW + i) * 256] = v[i];
         const uint32_t s8 = (klen & 3u) * 8u, q = klen >> 2;
         const int base = (hi ? 13 : -3) - (int)q;
         uint32_t t[17];
@@ -198,7 +201,7 @@ struct StrReader {
         for (int k = 0; k < 17; k++) {
             int i = base + k;
             i = i < -1 ? -1 : i;
-            i = i > NSTR - 1 ? NSTR - 1 : i;
+            i = i > NSTR - 1 ? (NV < 16 ? -1 : NSTR - 1) : i;
             t[k] = col[(i + 1) * 256];
         }
 #pragma unroll

@@ -181,6 +181,13 @@ int value_row(const rh_schema &s) {
 bool is_var(const rh_schema &s) { return s.value_kind == RH_VAL_VARBYTES; }
 // short string keys in fixed-width rows: RH_KEY_BYTES rows of that width to everything but the lift
 bool is_str(const rh_schema &s) { return s.key_kind == RH_KEY_STR; }
+// the value kinds a string key takes beside VARBYTES: (), u32, u64 (lift_strfix.hpp)
+bool str_fixed_value(const rh_schema &s) {
+    return s.value_kind == RH_VAL_UNIT || s.value_kind == RH_VAL_U32 || s.value_kind == RH_VAL_U64;
+}
+const char *const STR_VALUE_KINDS =
+    "RH_KEY_STR keys take RH_VAL_UNIT, RH_VAL_U32, RH_VAL_U64 or RH_VAL_VARBYTES values (a byte array under a string "
+    "key is VARBYTES with equal lengths); canonical-encode other maps on the host and use rh_lift_encoded_async";
 const rh_var_values *var_of(const rh_columns &c) { return static_cast<const rh_var_values *>(c.values); }
 
 int check_schema(const rh_schema *s) {
@@ -286,10 +293,23 @@ int lift_dispatch(const rh_schema &s, const rh_columns &c, size_t n, uint8_t *fp
                   const uint32_t *dst2 = nullptr) {
     bool supported = false;
     if (dst_row && (bs || dual)) return fail(RH_ERR_STATE, "lift to sorted rows: no block sums (internal error)");
+    if (is_str(s) && !is_var(s)) {
+        if (!str_fixed_value(s)) return fail(RH_ERR_UNSUPPORTED, STR_VALUE_KINDS);
+        rh::DevCols dc = to_dev(c);
+        dc.dst = dst_row;
+        dc.dst2 = dst2;
+        // one launch per lift (lift_strfix.hpp); the dual lift two passes, as for the other string shapes
+        const bool tags = c.tags != nullptr && s.record_kind != RH_REC_PLAIN;
+        hipError_t ev = rh::launch_lift_str_fixed((int)s.key_len, s.value_kind, s.record_kind, tags, dc, n, fps, bs, st,
+                                                  &supported);
+        if (supported && ev == hipSuccess && dual)
+            ev = rh::launch_lift_str_fixed((int)s.key_len, s.value_kind, RH_REC_PROJECTION, tags, dc, n, fps2, bs2, st,
+                                           &supported);
+        if (!supported) return fail(RH_ERR_UNSUPPORTED, "RH_KEY_STR rows are 16, 32 or 64 bytes wide");
+        if (ev != hipSuccess) return fail(RH_ERR_HIP, std::string("lift launch: ") + hipGetErrorString(ev));
+        return RH_OK;
+    }
     if (is_str(s)) {
-        if (!is_var(s))
-            return fail(RH_ERR_UNSUPPORTED, "RH_KEY_STR keys take RH_VAL_VARBYTES values only; canonical-encode on "
-                                            "the host and use rh_lift_encoded_async");
         rh::VarCols dc = to_var_dev(s, c);
         dc.dst = dst_row;
         dc.dst2 = dst2;
@@ -391,6 +411,11 @@ struct DevBuf {
 namespace rh {
 int set_error(int code, const std::string &msg) { return fail(code, msg); }
 bool debug_fail_point(const char *name) { return fail_point(name); }
+int check_str_rows(const rh_schema &s, const void *keys, size_t n) {
+    rh_columns h{};
+    h.keys = keys;
+    return check_str_host(is_str(s), (size_t)key_row(s), h, n);
+}
 }  // namespace rh
 
 // ---- dispatch table over the instantiated shapes (schemas.def) -------------------------------
@@ -486,7 +511,7 @@ int rh_schema_supported(const rh_schema *schema) {
     int rc = check_schema(schema);
     if (rc) return rc;
     const rh_schema &s = *schema;
-    if (is_str(s)) return is_var(s) && rh::str_key_supported(key_row(s)) ? 1 : 0;
+    if (is_str(s)) return (is_var(s) || str_fixed_value(s)) && rh::str_key_supported(key_row(s)) ? 1 : 0;
     if (is_var(s)) return rh::var_key_supported(s.key_kind, key_row(s)) ? 1 : 0;
     return rh::schema_instantiated(s.key_kind, (int)s.key_len, s.value_kind, (int)s.value_len) ? 1 : 0;
 }
@@ -738,8 +763,10 @@ extern "C" int rh_lift_host(int device, const rh_schema *schema, const rh_column
     if (is_var(*schema))
         return fail(RH_ERR_UNSUPPORTED, "rh_lift_host does not take VARBYTES values: lift on the device "
                                         "(rh_lift_records_async) or through a store");
+    if (is_str(*schema) && !str_fixed_value(*schema)) return fail(RH_ERR_UNSUPPORTED, STR_VALUE_KINDS);
     if (n == 0) return RH_OK;
     if (!host_fps) return fail(RH_ERR_ARG, "host_fps is NULL");
+    if ((rc = check_str_host(is_str(*schema), key_row(*schema), *h, n))) return rc;
     RH_HIP(hipSetDevice(device));
     HostPipe &p = host_pipe(device);
     std::lock_guard<std::mutex> g(p.mu);
@@ -1106,6 +1133,9 @@ struct rh_store {
     uint64_t small_limit() const {
         if (schema.key_kind == RH_KEY_UNIT) return 0;
         if (is_var(schema)) return 0;  // k_small_batch is not built for ragged values: the large-batch route
+        // ... nor for strings: to it a string row with a fixed-width value is a b16 / b32 row, and it
+        // would hash the row where the string is meant
+        if (str_keys) return 0;
         return std::min<uint64_t>(small_env, rh::small_batch_max((int)kl));
     }
     PinnedVec<uint8_t> sb_in;    // a small host batch, packed (the device reads it in place)
@@ -2509,7 +2539,8 @@ struct rh_store {
         if (pre_minmax) *pre_minmax = false;
         const uint32_t *pos = scratch.u32(7, m);
         if (scratch.err) return fail(RH_ERR_OOM, "scratch allocation failed");
-        if (fused_lift_search && !is_var(schema)) {  // (k_lift_search is not built for ragged values)
+        // (k_lift_search is not built for ragged values, nor for strings: it hashes the row, not the string)
+        if (fused_lift_search && !is_var(schema) && !str_keys) {
             rh::DevCols dc = to_dev(c);
             dc.dst = pos;
             dc.dst2 = sort_s2o;
@@ -3596,9 +3627,8 @@ int rh_store_create(int device, const rh_schema *schema, rh_store **out) {
     int rc = check_schema(schema);
     if (rc) return rc;
     if (!out) return fail(RH_ERR_ARG, "out is NULL");
-    if (is_str(*schema) && !is_var(*schema))
-        return fail(RH_ERR_UNSUPPORTED, "RH_KEY_STR keys take RH_VAL_VARBYTES values only (other maps with string "
-                                        "keys: the encoded store)");
+    if (is_str(*schema) && !is_var(*schema) && !str_fixed_value(*schema))
+        return fail(RH_ERR_UNSUPPORTED, STR_VALUE_KINDS);
     if (rh_schema_supported(schema) != 1)
         return fail(RH_ERR_UNSUPPORTED, "store needs a schema with a specialised lift kernel");
     // string rows sort, search and merge as byte rows of their width
@@ -4337,6 +4367,9 @@ int rh_snapshot_decode_device(const rh_schema *schema, int key_form, const void 
     if (rc) return rc;
     if (is_var(*schema))
         return fail(RH_ERR_UNSUPPORTED, "snapshot decode does not take VARBYTES values (fixed-width value columns only)");
+    // a file's String / Vec keys have per-entry lengths, which the fixed-stride locate cannot walk
+    if (is_str(*schema))
+        return fail(RH_ERR_UNSUPPORTED, "snapshot decode does not take RH_KEY_STR keys (keys of per-entry length in the file)");
     if ((!dev_bytes && len) || !o) return fail(RH_ERR_ARG, "NULL");
     if (!aligned16(dev_bytes)) return fail(RH_ERR_ARG, "snapshot bytes must be 16-byte aligned");
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -4376,6 +4409,9 @@ int rh_store_load_snapshot(rh_store *dated, rh_store *proj, int key_form, const 
     if (!bytes && len) return fail(RH_ERR_ARG, "bytes is NULL");
     if (is_var((dated ? dated : proj)->schema) || (proj && is_var(proj->schema)))
         return fail(RH_ERR_UNSUPPORTED, "snapshot reload does not take VARBYTES values (fixed-width value columns only)");
+    // (to the decode such a store's rows would be RH_FORM_VEC keys of the row width)
+    if ((dated ? dated : proj)->str_keys || (proj && proj->str_keys))
+        return fail(RH_ERR_UNSUPPORTED, "snapshot reload does not take RH_KEY_STR keys (keys of per-entry length in the file)");
     if (dated && dated->schema.record_kind != RH_REC_DATED) return fail(RH_ERR_ARG, "dated store must be DATED");
     if (proj && proj->schema.record_kind != RH_REC_PROJECTION)
         return fail(RH_ERR_ARG, "projection store must be PROJECTION");

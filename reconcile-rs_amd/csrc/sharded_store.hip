@@ -41,6 +41,9 @@
 namespace rh {
 int set_error(int code, const std::string &msg);  // rsos_hip_abi.hip: the calling thread's rh_last_error
 bool debug_fail_point(const char *name);          // rh_debug_fail_point, armed on the calling thread
+// host key rows of a RH_KEY_STR schema (length byte, zero padding), RH_ERR_ARG naming the first bad
+// row; RH_OK for every other key kind.  Checked here for the whole batch before any shard changes
+int check_str_rows(const rh_schema &s, const void *keys, size_t n);
 // rh_store_protocol_round in two halves (rsos_hip_abi.hip round_entry): a device round issued
 // (*pending: the store stays locked) and completed later on the same thread
 int store_round_issue(rh_store *s, int policy, uint64_t fan_out, const rh_segments *active, rh_segments *children,
@@ -1157,6 +1160,7 @@ int rh_sstore_set_splitters(rh_sstore *s, const void *keys) {
 int rh_sstore_load(rh_sstore *s, const rh_columns *h, size_t n) {
     if (!s || !h) return fail(RH_ERR_ARG, "NULL");
     if (n && s->kl && !h->keys) return fail(RH_ERR_ARG, "keys column is NULL");
+    if (int rc = rh::check_str_rows(s->schema, h->keys, n)) return rc;
     std::lock_guard<std::mutex> g(s->mu);
     const int G = s->G;
     const size_t kl = s->kl, vr = value_row(s->schema);
@@ -1217,6 +1221,7 @@ int rh_sstore_stage(rh_sstore *s, const rh_columns *h, const uint8_t *ops, size_
     std::lock_guard<std::mutex> g(s->mu);
     int rc;
     if ((rc = s->health())) return rc;
+    if ((rc = rh::check_str_rows(s->schema, h->keys, m))) return rc;
     const uint8_t *keys = static_cast<const uint8_t *>(h->keys);
     for (size_t i = 0; i < m; i++)
         if (ops[i] > 1) return fail(RH_ERR_ARG, "op must be 0 (insert) or 1 (delete)");
@@ -1261,6 +1266,7 @@ int rh_sstore_apply(rh_sstore *s, const rh_columns *h, const uint8_t *ops, size_
     // every check a shard's apply makes on the arguments, made here before any shard changes
     for (size_t i = 0; i < m; i++)
         if (ops[i] > 1) return fail(RH_ERR_ARG, "op must be 0 (insert) or 1 (delete)");
+    if ((rc = rh::check_str_rows(s->schema, h->keys, m))) return rc;
     if (m) {
         const rh_schema &sc = s->schema;
         if (sc.value_kind != RH_VAL_UNIT && !h->values) return fail(RH_ERR_ARG, "values column is NULL");

@@ -62,7 +62,7 @@ def encode_row(schema: RecordSchema, value) -> Tuple[bytes, int, int, int, int]:
         vb = b"" if e.tombstone else (e.value.encode() if isinstance(e.value, str) else bytes(e.value))
         return vb, e.phys, e.logical, e.node, 1 if e.tombstone else 0
     if e.tombstone:
-        if e.value not in (b"", 0, None):
+        if e.value not in (b"", 0, None, ()):
             raise ValueError("a tombstone carries no value bytes")
         vb = bytes(vr)
     elif isinstance(e.value, int):
@@ -70,7 +70,7 @@ def encode_row(schema: RecordSchema, value) -> Tuple[bytes, int, int, int, int]:
             raise ValueError("an integer value needs a u32 / u64 value column")
         vb = int(e.value).to_bytes(vr, "little")
     else:
-        vb = bytes(e.value)
+        vb = b"" if e.value is None or e.value == () else bytes(e.value)  # (None / (): a unit value)
         if len(vb) != vr:
             raise ValueError(f"value encodes to {len(vb)} bytes; the value column holds exactly {vr}")
     return vb, e.phys, e.logical, e.node, 1 if e.tombstone else 0

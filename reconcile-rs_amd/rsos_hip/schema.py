@@ -27,7 +27,8 @@ class RecordSchema:
         Vec<u8> / String of a length that differs per record (a heap and offsets, VAL_VARBYTES);
         key 'str15' / 'str31' / 'str63': String / Vec<u8> of at most 15 / 31 / 63 bytes in a 16- / 32- /
         64-byte row
-        (KEY_STR, strkeys.pack_str_keys), with 'var' values."""
+        (KEY_STR, strkeys.pack_str_keys), with 'var', 'unit', 'u32' or 'u64' values (a byte array
+        under a string key is 'var' with equal lengths)."""
         kk, kl = _kind(key, True)
         vk, vl = _kind(value, False)
         return RecordSchema(kk, kl, vk, vl, A.REC_PLAIN)

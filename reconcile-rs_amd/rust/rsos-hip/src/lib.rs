@@ -29,7 +29,13 @@
 //! map of a reference `FingerprintTreeMap<String, String>` whose keys are at most 63 (31, 15)
 //! bytes -- Kubernetes object names fit the 64-byte row: same fingerprints,
 //! same order (`strkey.rs`, `RH_KEY_STR`), with rounds, staged inserts and the host tier as for any
-//! fixed-width key.  Keys of 64 bytes or more take [`HipEncodedMap`].
+//! fixed-width key.  The fixed-width values `()`, `u32` / `i32` and `u64` / `i64` go under string
+//! keys too -- `HipFingerprintMap<ShortString<16>, u32>` is the reference's
+//! `FingerprintTreeMap<String, u32>`, `HipFingerprintMap<ShortString<64>, Entry<Timestamp, ()>>` the
+//! map behind a `ReplicatedSet<String>`, `ShortString<32> -> u64` a table of counters -- and so do
+//! their [`HipShardedMap`] counterparts; a `[u8; N]` / `FixedBytes<N>` value under a string key is
+//! not a column-store shape (use `Vec<u8>`, which encodes to the same bytes).  Keys of 64 bytes or
+//! more take [`HipEncodedMap`].
 
 mod encoded;
 mod ffi;
@@ -110,8 +116,8 @@ pub struct RecordRow {
 /// (`VALUE_KIND` = `RH_VAL_VARBYTES`, `VALUE_LEN` = 0: `String` / `Vec<u8>` values) a fixed-width key
 /// with a value of any length per record.
 /// Implemented in this crate (values.rs) for `lww_register::Entry<Timestamp, V>` (RECORD_KIND =
-/// DATED) and `State<V>` (PROJECTION) over any `V: FixedValue`, and for plain `u32` / `u64` /
-/// `FixedBytes<N>` values (PLAIN).  `write` must produce exactly the fields `rsos::encoding` would
+/// DATED) and `State<V>` (PROJECTION) over any `V: FixedValue`, and for plain `()` / `u32` / `i32` /
+/// `u64` / `i64` / `String` / `Vec<u8>` / `FixedBytes<N>` values (PLAIN).  `write` must produce exactly the fields `rsos::encoding` would
 /// serialise; the library's tests pin that equivalence.
 pub trait GpuRecord: Serialize {
     const VALUE_KIND: i32;

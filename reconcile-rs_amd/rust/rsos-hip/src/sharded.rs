@@ -9,7 +9,9 @@
 //! host thread each, and decomposes every question with no device-to-device traffic: sizes and
 //! ranks add up, an aggregate is the Add of the shards' parts (rsos/src/aggregate.rs:79-89), a
 //! protocol round's segments inside one shard are that shard's own round and the few that
-//! straddle a boundary are resolved from their two boundary shards.  The host keeps `K` and `V`
+//! straddle a boundary are resolved from their two boundary shards.  `ShortString<W>` keys with `()`,
+//! `u32` / `i32` or `u64` / `i64` values are sharded like any byte rows of width W (the default cut
+//! uses the leading 8 bytes; each shard lifts the strings); `String` / `Vec<u8>` values are not.  The host keeps `K` and `V`
 //! in its own rank-ordered index, as `HipFingerprintMap` does; every fingerprint is the GPU lift.
 
 use std::ops::{Bound, RangeBounds};

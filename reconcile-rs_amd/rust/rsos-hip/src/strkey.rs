@@ -9,6 +9,11 @@
 //! `[u8; W]` keys; only the lift hashes the string -- u64 length, then the bytes
 //! (rsos/src/encoding/serializer.rs:105-113) -- so the fingerprints are those of the reference's
 //! map over `String` / `Vec<u8>` keys.  Longer strings stay with the encoded map.
+//!
+//! Values under such keys: `String` / `Vec<u8>` (VARBYTES) and the `FixedValue` types `()`, `u32` /
+//! `i32`, `u64` / `i64`, plain or inside `Entry<Timestamp, V>` / `State<V>`; batches of a
+//! string-keyed map of any size take the library's large-batch route (its one-launch small-batch
+//! kernels hash the row, not the string).
 use serde::{Deserialize, Deserializer, Serialize, Serializer};
 
 use crate::{ffi, GpuKey};
@@ -104,6 +109,28 @@ short_string_key!(16 32 64);
 #[cfg(test)]
 mod tests {
     use super::*;
+
+    #[test]
+    fn fixed_width_values_under_string_keys() {
+        use crate::{schema, RecordRow};
+        use crate::GpuRecord;
+        use lww_register::{Entry, State, Timestamp};
+        let s = schema::<ShortString<16>, u32>();
+        assert_eq!((s.key_kind, s.key_len, s.value_kind, s.value_len, s.record_kind),
+                   (ffi::RH_KEY_STR, 16, ffi::RH_VAL_U32, 4, ffi::RH_REC_PLAIN));
+        let s = schema::<ShortString<32>, Entry<Timestamp, i64>>();
+        assert_eq!((s.key_len, s.value_kind, s.value_len, s.record_kind), (32, ffi::RH_VAL_U64, 8, ffi::RH_REC_DATED));
+        let s = schema::<ShortString<64>, State<()>>();
+        assert_eq!((s.key_len, s.value_kind, s.value_len, s.record_kind), (64, ffi::RH_VAL_UNIT, 0, ffi::RH_REC_PROJECTION));
+        let s = schema::<ShortString<64>, ()>();
+        assert_eq!((s.value_kind, s.value_len, s.record_kind), (ffi::RH_VAL_UNIT, 0, ffi::RH_REC_PLAIN));
+        let mut row = RecordRow::default();
+        (-2i32).write(&mut row);
+        assert_eq!(row.value, vec![0xfe, 0xff, 0xff, 0xff]);
+        let mut row = RecordRow::default();
+        ().write(&mut row);
+        assert!(row.value.is_empty());
+    }
 
     #[test]
     fn row_order_is_string_order() {

@@ -8,7 +8,9 @@
 //!   (lww-register/src/clock.rs:143-181) -> the phys / logical / node columns;
 //! * `State::Present(v)` = u32 variant 0 then `v`; `State::Tombstone` = u32 variant 1 -> the tag
 //!   column (the variant word is synthesised on the device);
-//! * `v`: a `u32` / `u64` is its LE bytes (value kinds U32 / U64, no prefix); a byte string
+//! * `v`: a `u32` / `i32` / `u64` / `i64` is its LE bytes (value kinds U32 / U64, no prefix; a signed
+//!   integer is its two's complement, encoding/serializer.rs:76-84); `()` is no bytes at all (UNIT);
+//!   a byte string
 //!   (`Vec<u8>`, `String`, `[u8; N]`, `FixedBytes<N>`) is a u64 length prefix then the bytes
 //!   (encoding/serializer.rs:105-113, :162-179) -> value kind BYTES, the prefix synthesised;
 //!   a `Vec<u8>` / `String` itself, whose length differs per record -> value kind VARBYTES: the
@@ -25,7 +27,7 @@ use crate::{ffi, GpuRecord, RecordRow};
 /// A value type the device hashes from one value column: fixed-width, or (VARBYTES) a heap of
 /// byte strings of per-record length.
 pub trait FixedValue: Serialize {
-    /// `RH_VAL_U32`, `RH_VAL_U64`, `RH_VAL_BYTES` or `RH_VAL_VARBYTES`
+    /// `RH_VAL_UNIT`, `RH_VAL_U32`, `RH_VAL_U64`, `RH_VAL_BYTES` or `RH_VAL_VARBYTES`
     const KIND: i32;
     /// Bytes of the value column (for BYTES: the byte string's length, without its prefix; 0 for
     /// VARBYTES, whose lengths travel as offsets).
@@ -43,6 +45,23 @@ impl FixedValue for u32 {
 }
 
 impl FixedValue for u64 {
+    const KIND: i32 = ffi::RH_VAL_U64;
+    const LEN: u32 = 8;
+    fn column(&self, out: &mut Vec<u8>) {
+        out.extend_from_slice(&self.to_le_bytes());
+    }
+}
+
+// i32 / i64: the LE bytes of the two's complement, the columns of u32 / u64
+impl FixedValue for i32 {
+    const KIND: i32 = ffi::RH_VAL_U32;
+    const LEN: u32 = 4;
+    fn column(&self, out: &mut Vec<u8>) {
+        out.extend_from_slice(&self.to_le_bytes());
+    }
+}
+
+impl FixedValue for i64 {
     const KIND: i32 = ffi::RH_VAL_U64;
     const LEN: u32 = 8;
     fn column(&self, out: &mut Vec<u8>) {
@@ -181,6 +200,8 @@ impl<V: FixedValue> GpuRecord for State<V> {
 }
 
 // A plain `FingerprintTreeMap<K, V>` (benches/bench.rs:47-92 fills `u32 -> u32`): `lift(k, v)`.
+// With `ShortString<W>` keys these are the reference's `FingerprintTreeMap<String, u32>` and
+// `<&str, u32>` (fingerprint_tree_map/tests/basic.rs:205,226), and `()` a plain set of names.
 macro_rules! plain_record {
     ($($t:ty)*) => {$(
         impl GpuRecord for $t {
@@ -193,7 +214,7 @@ macro_rules! plain_record {
         }
     )*};
 }
-plain_record!(u32 u64 String Vec<u8>);
+plain_record!(() u32 i32 u64 i64 String Vec<u8>);
 
 impl<const N: usize> GpuRecord for FixedBytes<N> {
     const VALUE_KIND: i32 = ffi::RH_VAL_BYTES;
