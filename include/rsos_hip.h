@@ -95,10 +95,11 @@ typedef enum rh_status {
  * host batch's key rows are validated for the whole batch before any shard changes).  Batches of a
  * STR store of any size take the large-batch route with separate lift and search launches: the
  * fused lift + search kernel and the small-batch kernel hash the row, not the string, and are not
- * built for strings (rh_store_batch_stats: small_batches stays 0).  Not supported
- * (RH_ERR_UNSUPPORTED, the message names RH_KEY_STR): rh_store_load_snapshot into such a store and
- * rh_snapshot_decode_device with a STR schema -- a file's String / Vec keys have per-entry
- * lengths, which the fixed-stride locate cannot walk.
+ * built for strings (rh_store_batch_stats: small_batches stays 0).  Snapshot reload is built
+ * behind a flag: rh_store_load_snapshot into such a store and rh_snapshot_decode_device with a STR
+ * schema take key_form RH_FORM_VEC | RH_FORM_RAGGED (the byte-granular locate, "snapshot reload"
+ * below).  Without the flag both stay RH_ERR_UNSUPPORTED (the message names RH_KEY_STR): a file's
+ * String / Vec keys have per-entry lengths, which the fixed-stride locate cannot walk.
  * 64-byte rows and the one-launch kernels: the store's small questions (rh_store_ranks / _select /
  * _keys of at most 64 entries, rh_store_aggregate_keys) and its protocol rounds of at most 16
  * segments are served, for rows of at most 32 bytes, by kernels that carry the keys inline in
@@ -168,9 +169,10 @@ typedef struct rh_columns {
  * _load_device / _apply / _apply_device / _apply_device_many / _stage; every store question works
  * as for any other value kind (values never take part in them).  Batches of this kind of any size
  * take the large-batch route with separate lift and search launches: the fused lift + search
- * kernel and the small-batch kernel are not built for it.  Not supported (RH_ERR_UNSUPPORTED,
- * the message names VARBYTES): rh_sstore_create (refused before any device call),
- * rh_store_load_snapshot, rh_snapshot_decode_device and rh_lift_host.                          */
+ * kernel and the small-batch kernel are not built for it.  rh_store_load_snapshot and
+ * rh_snapshot_decode_device take it with RH_FORM_RAGGED in key_form ("snapshot reload" below).
+ * Not supported (RH_ERR_UNSUPPORTED, the message names VARBYTES): rh_sstore_create (refused before
+ * any device call), rh_lift_host, and the two snapshot calls without that flag.                */
 typedef struct rh_var_values {
     const uint8_t  *bytes;     /* the value heap                                              */
     const uint64_t *offsets;   /* n + 1 entries, non-decreasing                               */
@@ -478,8 +480,26 @@ int rh_store_batch_stats(rh_store *store, uint64_t *small_batches, uint64_t *lar
  * Keys in the file: u32 / u64 as fixed LE; byte keys as [u8; L] (RH_FORM_ARRAY, a bincode tuple:
  * the raw bytes) or Vec<u8> / String (RH_FORM_VEC: u64 length L, then the bytes).  Values of
  * kind BYTES are Vec<u8> (u64 length, then the bytes).  Key and value lengths must be
- * multiples of 4 (RH_ERR_UNSUPPORTED otherwise).                                            */
-typedef enum rh_key_form { RH_FORM_ARRAY = 0, RH_FORM_VEC = 1 } rh_key_form;
+ * multiples of 4 (RH_ERR_UNSUPPORTED otherwise).
+ *
+ * RH_FORM_RAGGED is a flag OR-ed with RH_FORM_ARRAY or RH_FORM_VEC (key_form 2 or 3; any value
+ * outside 0..3 is RH_ERR_ARG "bad key_form").  With it both calls below locate the entries byte by
+ * byte -- an entry's length is read from its own bytes -- and take every schema for which
+ * rh_schema_supported returns 1:
+ *   - RH_KEY_STR keys, RH_FORM_VEC | RH_FORM_RAGGED only (with RH_FORM_ARRAY: RH_ERR_ARG): in the
+ *     file a u64 LE length L, then L bytes (bincode String / Vec<u8>); in the columns and the store
+ *     the padded row described at rh_key_kind.  An entry with L > W - 1 is RH_ERR_DATA; the message
+ *     names the entry's index, L and W.
+ *   - RH_VAL_VARBYTES values under any key kind: a present entry holds a u64 LE length M, then M
+ *     bytes; a tombstone nothing after the variant.
+ *   - fixed-width keys and values as without the flag, of any length (no multiple-of-4 rule), with
+ *     the same store contents as the flag-clear route gives for the same file.
+ * Errors, atomicity and rh_snapshot_info are the same on both routes: a corrupt file is RH_ERR_DATA
+ * before either store changes; entries_end is the exact offset of PersistedState.members (what
+ * follows the n-th entry is never parsed as an entry); fewer than 2^31 entries.  Without the flag
+ * nothing changes: RH_KEY_STR stores and VARBYTES schemas are refused (RH_ERR_UNSUPPORTED) before
+ * the bytes are looked at.                                                                   */
+typedef enum rh_key_form { RH_FORM_ARRAY = 0, RH_FORM_VEC = 1, RH_FORM_RAGGED = 2 } rh_key_form;
 
 typedef struct rh_snapshot_info {
     uint64_t entries;     /* PersistedState.entries.len()                                  */
@@ -493,7 +513,16 @@ typedef struct rh_snapshot_info {
 int rh_snapshot_header(const void *bytes, size_t len, uint64_t *entries);
 /* Decode the entries of a device-resident snapshot into device columns with room for `cap`
  * rows.  keys / phys / logical / node / tags / values are all written (a tombstone's value
- * row is zero-filled; tags = the State variant).  Synchronous on `stream`.                */
+ * row is zero-filled; tags = the State variant).  Synchronous on `stream`.
+ * RH_VAL_VARBYTES (RH_FORM_RAGGED only): dev_out->values points to a HOST rh_var_values whose
+ * bytes and offsets are WRITABLE device buffers -- bytes 4-byte aligned, bytes_len (the heap's
+ * capacity) a multiple of 4, offsets 8-byte aligned with room for cap + 1 entries.  The call
+ * writes offsets[0 .. n] and the values packed in file order, value i at bytes[offsets[i] ..
+ * offsets[i + 1]), a tombstone's span empty, and zeroes the bytes from offsets[n] to the next
+ * multiple of 4: the columns can go to rh_lift_records_async / rh_store_load_device as they are.
+ * If the values need more than bytes_len bytes the call returns RH_ERR_ARG, and nothing is
+ * promised about the contents of any output buffer (none is written out of bounds).  A heap of
+ * len bytes (rounded up to 4) always suffices.                                              */
 int rh_snapshot_decode_device(const rh_schema *schema, int key_form, const void *dev_bytes, size_t len,
                               const rh_columns *dev_out, size_t cap, rh_snapshot_info *info, void *stream);
 /* Reload: replace the contents of `dated` (record_kind DATED) and / or `projection`
@@ -634,9 +663,16 @@ int rh_debug_fail_point(const char *name);
  * loading store's stream; rh_debug_last_reload_us reads the last reload's times back in
  * microseconds: locate = the entry walk and the transfer-function tree, lift = the fused pass
  * (listing, both lifts, keys, samples and block sums; snapshot reloads of records up to 192 B).
- * Both are 0 until a timed reload has run.                                                  */
+ * Both are 0 until a timed reload has run.  A RH_FORM_RAGGED reload: locate = the guess, the
+ * fix-up rounds, the scan and the decode into columns (value bytes included); lift = the lifts
+ * and the loads' enqueued sums.                                                              */
 int rh_debug_reload_timing(int on);
 int rh_debug_last_reload_us(double *locate_us, double *lift_us);
+/* The calling thread's last RH_FORM_RAGGED decode or reload: the segment size in bytes, the
+ * number of segments the file was cut into, the fix-up rounds run (the last one changes
+ * nothing) and the segments walked again in them, summed over the rounds.  Before any such call:
+ * the segment size a call would use, and zeros.  For tests and measurement.                  */
+int rh_debug_ragged_stats(uint64_t *segment_bytes, uint64_t *segments, uint64_t *rounds, uint64_t *rewalked);
 /* on != 0: time every following large batch's fused lift + search launch (k_lift_search, the
  * batch path's dominant kernel) with HIP events on the store's stream, accumulated over every
  * store; rh_debug_batch_kernel_us reads the sum (microseconds) and the number of timed launches,

@@ -31,6 +31,7 @@
 #include "host_tier.hpp"
 #include "lift_kernels.hpp"
 #include "small_batch.hpp"
+#include "snap_ragged.hpp"
 #include "snapshot_kernels.hpp"
 #include "store_kernels.hpp"
 
@@ -4352,6 +4353,202 @@ int snapshot_reload_fused(rh_store *dated, rh_store *proj, int mode, const rh::S
     return RH_OK;
 }
 
+// ---- the RH_FORM_RAGGED route (snap_ragged.hpp): entries whose lengths are in their own bytes ----
+// rh_debug_ragged_stats: the calling thread's last ragged decode or reload
+thread_local uint64_t g_rag_stats[4] = {0, 0, 0, 0};
+
+int ragged_format(const rh_schema &s, int form, size_t len, uint64_t n, rh::RagFmt *f) {
+    if (is_str(s) && form != RH_FORM_VEC)
+        return fail(RH_ERR_ARG, "RH_KEY_STR keys are Vec / String keys in the file (u64 length, then the bytes): "
+                                "RH_FORM_VEC | RH_FORM_RAGGED");
+    if (form == RH_FORM_VEC && s.key_kind != RH_KEY_BYTES && !is_str(s))
+        return fail(RH_ERR_ARG, "RH_FORM_VEC needs byte keys");
+    if (rh_schema_supported(&s) != 1)
+        return fail(RH_ERR_UNSUPPORTED, "no specialised lift kernel for this schema; canonical-encode on the host and "
+                                        "use rh_lift_encoded_async");
+    f->len = len;
+    f->key_mode = is_str(s) ? rh::RagFmt::KEY_STR : form == RH_FORM_VEC ? rh::RagFmt::KEY_VEC : rh::RagFmt::KEY_RAW;
+    f->key_len = (uint32_t)key_row(s);
+    f->val_mode = is_var(s) ? rh::RagFmt::VAL_VAR : s.value_kind == RH_VAL_BYTES ? rh::RagFmt::VAL_VEC : rh::RagFmt::VAL_RAW;
+    f->val_len = (uint32_t)value_row(s);
+    if (f->key_len > 4096) return fail(RH_ERR_UNSUPPORTED, "snapshot keys too long for the device decoder");
+    const uint32_t kpre = f->key_mode != rh::RagFmt::KEY_RAW ? 8 : 0;
+    f->hdr = kpre + (is_str(s) ? f->key_len - 1 : f->key_len) + 24 + (f->val_mode != rh::RagFmt::VAL_RAW ? 8 : 0);
+    f->min_entry = kpre + (is_str(s) ? 0 : f->key_len) + 24;
+    f->seg = rh::ragged_segment_bytes();
+    if (n >= (1ull << 31)) return fail(RH_ERR_UNSUPPORTED, "snapshot has more than 2^31 entries");
+    if (n > (len - 16) / f->min_entry)
+        return fail(RH_ERR_DATA, "snapshot entry count " + std::to_string(n) + " exceeds what its " +
+                                     std::to_string(len) + " bytes can hold (io error: unexpected end of file)");
+    return RH_OK;
+}
+
+// Locate and decode entries [0, n) into the columns of `o` (VARBYTES: o.values is the host
+// descriptor of a writable device heap of bytes_len bytes and n + 1 offsets).  fit: check the
+// values against bytes_len first (a read-back); a reload's heap is as long as the file.
+// Synchronises st.
+int ragged_decode_into(const rh_schema &s, int form, const uint8_t *dev, size_t len, uint64_t n, const rh_columns &o,
+                       bool fit, rh::Scratch &scr, hipStream_t st, rh_snapshot_info *info) {
+    rh::RagFmt f;
+    int rc = ragged_format(s, form, len, n, &f);
+    if (rc) return rc;
+    g_rag_stats[0] = f.seg, g_rag_stats[1] = (len + f.seg - 1) / f.seg, g_rag_stats[2] = 0, g_rag_stats[3] = 0;
+    const rh_var_values *v = is_var(s) ? var_of(o) : nullptr;
+    info->entries = n;
+    info->keys = n;
+    info->tombstones = 0;
+    info->entries_end = 16;
+    if (n == 0) {
+        if (v && v->offsets) RH_HIP(hipMemsetAsync(const_cast<uint64_t *>(v->offsets), 0, 8, st));
+        RH_HIP(hipStreamSynchronize(st));
+        return RH_OK;
+    }
+    rh::RagTables t;
+    rh::RagResult res;
+    RH_HIP(rh::ragged_locate(f, dev, n, scr, st, &t, &res));
+    if (scr.err) return fail(RH_ERR_OOM, "scratch allocation failed");
+    g_rag_stats[2] = res.rounds, g_rag_stats[3] = res.rewalked;
+    if (res.parsed < n) {
+        const std::string at = "entry " + std::to_string(res.parsed) + " at offset " + std::to_string(res.bad_pos);
+        if (res.why == rh::RAG_KEY_LEN && is_str(s))
+            return fail(RH_ERR_DATA, "snapshot " + at + ": key length " + std::to_string(res.bad_len) +
+                                         " does not fit a RH_KEY_STR row of width " + std::to_string(f.key_len) +
+                                         " (at most " + std::to_string(f.key_len - 1) + " bytes)");
+        const std::string why = res.why == rh::RAG_KEY_LEN   ? "key length " + std::to_string(res.bad_len) + " differs from the schema's"
+                                : res.why == rh::RAG_VAL_LEN ? "value length " + std::to_string(res.bad_len) + " differs from the schema's"
+                                : res.why == rh::RAG_VARIANT ? "invalid State variant, expected variant index 0 <= i < 2"
+                                                             : "io error: unexpected end of file";
+        return fail(RH_ERR_DATA, "snapshot entries are corrupt: " + std::to_string(res.parsed) + " of " + std::to_string(n) +
+                                     " entries parse (" + at + ": " + why + ")");
+    }
+    rh::RagCols c;
+    c.keys = (uint8_t *)o.keys;
+    c.phys = (uint64_t *)o.phys;
+    c.logical = (uint32_t *)o.logical;
+    c.node = (uint64_t *)o.node;
+    c.tags = (uint8_t *)o.tags;
+    c.values = v ? const_cast<uint8_t *>(v->bytes) : (uint8_t *)o.values;
+    c.voffs = v ? const_cast<uint64_t *>(v->offsets) : nullptr;
+    c.heap_cap = v ? v->bytes_len : 0;
+    RH_HIP(rh::ragged_decode(f, dev, n, t, res, c, scr, st));
+    if (scr.err) return fail(RH_ERR_OOM, "scratch allocation failed");
+    if (v && fit) {
+        uint64_t total = 0;
+        RH_HIP(hipMemcpyAsync(&total, c.voffs + n, 8, hipMemcpyDeviceToHost, st));
+        RH_HIP(hipStreamSynchronize(st));
+        if (total > v->bytes_len)
+            return fail(RH_ERR_ARG, "VARBYTES: the snapshot's values take " + std::to_string(total) +
+                                        " bytes, more than bytes_len " + std::to_string(v->bytes_len));
+    }
+    RH_HIP(rh::ragged_copy_values(f, dev, n, c, scr, st));
+    unsigned long long w[rh::RAGW_N];
+    RH_HIP(hipMemcpyAsync(w, t.words, sizeof w, hipMemcpyDeviceToHost, st));
+    RH_HIP(hipStreamSynchronize(st));
+    info->tombstones = w[rh::RAGW_TOMB];
+    info->entries_end = w[rh::RAGW_END];
+    return RH_OK;
+}
+
+// rh_store_load_snapshot with RH_FORM_RAGGED: the non-fused reload, the ragged decode in the
+// place of snapshot_decode_into.  The caller holds both stores' locks and has checked the pair.
+int snapshot_reload_ragged(rh_store *dated, rh_store *proj, int form, const void *bytes, size_t len, int on_device,
+                           rh_snapshot_info *info, void *after_stream) {
+    rh_store *a = dated ? dated : proj;
+    rh_schema ds = a->lift_schema();
+    ds.record_kind = RH_REC_DATED;
+    int rc;
+    if (is_str(ds) && form != RH_FORM_VEC) return ragged_format(ds, form, 16, 0, nullptr);
+    uint8_t h[16] = {0};
+    const size_t hl = std::min<size_t>(len, 16);
+    if (on_device) {
+        if (!aligned16(bytes)) return fail(RH_ERR_ARG, "snapshot bytes must be 16-byte aligned");
+        if ((rc = a->after(after_stream))) return rc;
+        if (hl) RH_HIP(hipMemcpyAsync(h, bytes, hl, hipMemcpyDeviceToHost, a->stream));
+        RH_HIP(hipStreamSynchronize(a->stream));
+    } else if (hl) {
+        memcpy(h, bytes, hl);
+    }
+    uint64_t n = 0;
+    if ((rc = snapshot_header(h, len, &n))) return rc;
+    rh::RagFmt f;
+    if ((rc = ragged_format(ds, form, len, n, &f))) return rc;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    struct EvGuard {
+        hipEvent_t *e;
+        ~EvGuard() {
+            for (int k = 0; k < 3; k++)
+                if (e[k]) (void)hipEventDestroy(e[k]);
+        }
+    } ev_guard{ev};
+    if (g_time_reload.load()) {
+        for (auto &e : ev) RH_HIP(hipEventCreate(&e));
+        RH_HIP(hipEventRecord(ev[0], a->stream));
+    }
+    const uint8_t *dev = static_cast<const uint8_t *>(bytes);
+    if (!on_device) {
+        if ((rc = a->snap.ensure(len + 16))) return rc;
+        RH_HIP(hipMemcpyAsync(a->snap.p, bytes, len, hipMemcpyHostToDevice, a->stream));
+        dev = a->snap.p;
+    }
+    DevColumns &stg = a->staging;
+    const size_t kr = key_row(ds), vr = value_row(ds);
+    // VARBYTES: the values cannot take more bytes than the file has, so the heap needs no read-back
+    const size_t heap = is_var(ds) ? (len + 3) & ~size_t(3) : n * vr;
+    if ((rc = stg.keys.ensure(n * kr + 16)) || (rc = stg.values.ensure(heap + 16)) || (rc = stg.phys.ensure(n + 1)) ||
+        (rc = stg.node.ensure(n + 1)) || (rc = stg.logical.ensure(n + 1)) || (rc = stg.tags.ensure(n + 16)) ||
+        (is_var(ds) && (rc = stg.voffs.ensure(n + 1))))
+        return rc;
+    stg.has_tags = true;
+    stg.var = rh_var_values{stg.values.p, stg.voffs.p, is_var(ds) ? heap : 0};
+    const rh_columns cols = stg.view(ds);
+    rh_snapshot_info inf{};
+    rc = ragged_decode_into(ds, form, dev, len, n, cols, false, a->scratch, a->stream, &inf);
+    if (!on_device) a->snap.release();
+    if (rc) return rc;
+    if (ev[1]) RH_HIP(hipEventRecord(ev[1], a->stream));
+    const bool dual = dated && proj && n;
+    if (dual) {
+        for (rh_store *x : {dated, proj})
+            if ((rc = x->bfps[x->cb].ensure(n * 32 + 64)) || (rc = x->bsums.ensure(rh_num_blocks(n) * 32 + 32)))
+                return rc;
+        if ((rc = lift_dispatch(ds, cols, n, dated->bfps[dated->cb].p, dated->bsums.p, proj->bfps[proj->cb].p,
+                                proj->bsums.p, true, a->stream)))
+            return rc;
+        if ((rc = proj->after(a->stream))) return rc;
+    }
+    // as the grid route: a failure in either half of either store leaves BOTH stores empty
+    for (rh_store *x : {dated, proj}) {
+        if (!x) continue;
+        if (x == proj && fail_point("snapshot.load_begin")) rc = fail(RH_ERR_OOM, "injected failure (load_begin)");
+        else rc = x->load_begin(cols, n, dual);
+        if (rc) break;
+    }
+    if (!rc && ev[2]) RH_HIP(hipEventRecord(ev[2], a->stream));
+    for (rh_store *x : {dated, proj}) {
+        if (rc) break;
+        if (!x) continue;
+        if (x == dated && fail_point("snapshot.load_finish")) rc = fail(RH_ERR_OOM, "injected failure (load_finish)");
+        else rc = x->load_finish(n, true);
+        inf.keys = x->nb;
+    }
+    if (rc) {
+        const std::string msg = g_err;
+        for (rh_store *x : {dated, proj})
+            if (x) x->reset_empty();
+        return fail(rc, msg);
+    }
+    if (ev[2]) {
+        float ms[2] = {0, 0};
+        RH_HIP(hipEventElapsedTime(&ms[0], ev[0], ev[1]));
+        RH_HIP(hipEventElapsedTime(&ms[1], ev[1], ev[2]));
+        std::lock_guard<std::mutex> g(g_reload_mu);
+        g_reload_us[0] = 1e3 * ms[0];
+        g_reload_us[1] = 1e3 * ms[1];
+    }
+    if (info) *info = inf;
+    return RH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -4365,11 +4562,14 @@ int rh_snapshot_decode_device(const rh_schema *schema, int key_form, const void 
                               const rh_columns *o, size_t cap, rh_snapshot_info *info, void *stream) {
     int rc = check_schema(schema);
     if (rc) return rc;
-    if (is_var(*schema))
-        return fail(RH_ERR_UNSUPPORTED, "snapshot decode does not take VARBYTES values (fixed-width value columns only)");
+    const bool ragged = key_form >= 0 && key_form <= 3 && (key_form & RH_FORM_RAGGED);
+    if (!ragged && is_var(*schema))
+        return fail(RH_ERR_UNSUPPORTED, "snapshot decode does not take VARBYTES values (fixed-width value columns only) "
+                                        "unless key_form has RH_FORM_RAGGED");
     // a file's String / Vec keys have per-entry lengths, which the fixed-stride locate cannot walk
-    if (is_str(*schema))
-        return fail(RH_ERR_UNSUPPORTED, "snapshot decode does not take RH_KEY_STR keys (keys of per-entry length in the file)");
+    if (!ragged && is_str(*schema))
+        return fail(RH_ERR_UNSUPPORTED, "snapshot decode does not take RH_KEY_STR keys (keys of per-entry length in the "
+                                        "file) unless key_form is RH_FORM_VEC | RH_FORM_RAGGED");
     if ((!dev_bytes && len) || !o) return fail(RH_ERR_ARG, "NULL");
     if (!aligned16(dev_bytes)) return fail(RH_ERR_ARG, "snapshot bytes must be 16-byte aligned");
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -4383,7 +4583,16 @@ int rh_snapshot_decode_device(const rh_schema *schema, int key_form, const void 
     if (n && ((key_row(*schema) && !o->keys) || (value_row(*schema) && !o->values) || !o->phys || !o->logical ||
               !o->node || !o->tags))
         return fail(RH_ERR_ARG, "output columns are NULL");
-    if (!aligned16(o->keys) || !aligned16(o->values) || !aligned16(o->phys) || !aligned16(o->node) ||
+    const bool var = is_var(*schema);
+    if (var) {  // the host descriptor of a writable device heap and cap + 1 offsets
+        const rh_var_values *v = var_of(*o);
+        if (!v || !v->offsets) return fail(RH_ERR_ARG, "VARBYTES: the output needs a rh_var_values with offsets");
+        if (v->bytes_len && !v->bytes) return fail(RH_ERR_ARG, "VARBYTES: bytes is NULL");
+        if (v->bytes_len % 4) return fail(RH_ERR_ARG, "VARBYTES: bytes_len must be a multiple of 4 (pad the heap)");
+        if (reinterpret_cast<uintptr_t>(v->bytes) % 4) return fail(RH_ERR_ARG, "VARBYTES: bytes must be 4-byte aligned");
+        if (reinterpret_cast<uintptr_t>(v->offsets) % 8) return fail(RH_ERR_ARG, "VARBYTES: offsets must be 8-byte aligned");
+    }
+    if (!aligned16(o->keys) || (!var && !aligned16(o->values)) || !aligned16(o->phys) || !aligned16(o->node) ||
         !aligned16(o->logical))
         return fail(RH_ERR_ARG, "device columns must be 16-byte aligned");
     // the decode tables are kept per device between calls (the call is synchronous, so the
@@ -4398,7 +4607,13 @@ int rh_snapshot_decode_device(const rh_schema *schema, int key_form, const void 
     scr.stream = st;
     scr.err = hipSuccess;
     rh_snapshot_info inf{};
-    rc = snapshot_decode_into(*schema, key_form, static_cast<const uint8_t *>(dev_bytes), len, n, *o, scr, st, &inf);
+    if (ragged) {
+        rh_schema ds = *schema;  // the file holds (K, Entry<Timestamp, V>) whatever the caller lifts
+        ds.record_kind = RH_REC_DATED;
+        rc = ragged_decode_into(ds, key_form & 1, static_cast<const uint8_t *>(dev_bytes), len, n, *o, true, scr, st, &inf);
+    } else {
+        rc = snapshot_decode_into(*schema, key_form, static_cast<const uint8_t *>(dev_bytes), len, n, *o, scr, st, &inf);
+    }
     if (!rc && info) *info = inf;
     return rc;
 }
@@ -4407,18 +4622,21 @@ int rh_store_load_snapshot(rh_store *dated, rh_store *proj, int key_form, const 
                            int on_device, rh_snapshot_info *info, void *after_stream) {
     if (!dated && !proj) return fail(RH_ERR_ARG, "no store given");
     if (!bytes && len) return fail(RH_ERR_ARG, "bytes is NULL");
-    if (is_var((dated ? dated : proj)->schema) || (proj && is_var(proj->schema)))
-        return fail(RH_ERR_UNSUPPORTED, "snapshot reload does not take VARBYTES values (fixed-width value columns only)");
+    const bool ragged = key_form >= 0 && key_form <= 3 && (key_form & RH_FORM_RAGGED);
+    if (!ragged && (is_var((dated ? dated : proj)->schema) || (proj && is_var(proj->schema))))
+        return fail(RH_ERR_UNSUPPORTED, "snapshot reload does not take VARBYTES values (fixed-width value columns only) "
+                                        "unless key_form has RH_FORM_RAGGED");
     // (to the decode such a store's rows would be RH_FORM_VEC keys of the row width)
-    if ((dated ? dated : proj)->str_keys || (proj && proj->str_keys))
-        return fail(RH_ERR_UNSUPPORTED, "snapshot reload does not take RH_KEY_STR keys (keys of per-entry length in the file)");
+    if (!ragged && ((dated ? dated : proj)->str_keys || (proj && proj->str_keys)))
+        return fail(RH_ERR_UNSUPPORTED, "snapshot reload does not take RH_KEY_STR keys (keys of per-entry length in the "
+                                        "file) unless key_form is RH_FORM_VEC | RH_FORM_RAGGED");
     if (dated && dated->schema.record_kind != RH_REC_DATED) return fail(RH_ERR_ARG, "dated store must be DATED");
     if (proj && proj->schema.record_kind != RH_REC_PROJECTION)
         return fail(RH_ERR_ARG, "projection store must be PROJECTION");
     if (dated && proj &&
         (dated->schema.key_kind != proj->schema.key_kind || dated->schema.key_len != proj->schema.key_len ||
          dated->schema.value_kind != proj->schema.value_kind || dated->schema.value_len != proj->schema.value_len ||
-         dated->device != proj->device))
+         dated->device != proj->device || dated->str_keys != proj->str_keys))
         return fail(RH_ERR_ARG, "dated and projection stores differ in key / value kind or device");
     rh_store *a = dated ? dated : proj;
     std::unique_lock<std::mutex> la(a->mu, std::defer_lock), lb;
@@ -4431,6 +4649,7 @@ int rh_store_load_snapshot(rh_store *dated, rh_store *proj, int key_form, const 
     RH_HIP(hipSetDevice(a->device));
     for (rh_store *x : {dated, proj})  // a reload replaces the contents: staged rows are superseded
         if (x) x->pend.clear();
+    if (ragged) return snapshot_reload_ragged(dated, proj, key_form & 1, bytes, len, on_device, info, after_stream);
     int rc;
     uint8_t h[16] = {0};
     const size_t hl = std::min<size_t>(len, 16);
@@ -4563,6 +4782,15 @@ int rh_debug_last_reload_us(double *locate_us, double *lift_us) {
     std::lock_guard<std::mutex> g(g_reload_mu);
     *locate_us = g_reload_us[0];
     *lift_us = g_reload_us[1];
+    return RH_OK;
+}
+
+int rh_debug_ragged_stats(uint64_t *segment_bytes, uint64_t *segments, uint64_t *rounds, uint64_t *rewalked) {
+    if (!segment_bytes || !segments || !rounds || !rewalked) return fail(RH_ERR_ARG, "NULL");
+    *segment_bytes = g_rag_stats[0] ? g_rag_stats[0] : rh::ragged_segment_bytes();
+    *segments = g_rag_stats[1];
+    *rounds = g_rag_stats[2];
+    *rewalked = g_rag_stats[3];
     return RH_OK;
 }
 

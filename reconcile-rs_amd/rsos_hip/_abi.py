@@ -19,6 +19,7 @@ VAL_UNIT, VAL_U32, VAL_U64, VAL_BYTES, VAL_VARBYTES = 0, 1, 2, 3, 4
 REC_PLAIN, REC_DATED, REC_PROJECTION = 0, 1, 2
 BLOCK, SUPER = 256, 65536
 FORM_ARRAY, FORM_VEC = 0, 1  # rh_key_form: [u8; L] | Vec<u8> / String
+FORM_RAGGED = 2  # flag OR-ed with either: the byte-granular locate (string keys, VARBYTES values)
 
 
 class Schema(C.Structure):
@@ -158,6 +159,8 @@ SIGNATURES = [
     ("rh_debug_fail_point", C.c_int, [C.c_char_p]),
     ("rh_debug_reload_timing", C.c_int, [C.c_int]),
     ("rh_debug_last_reload_us", C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("rh_debug_ragged_stats", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                        C.POINTER(C.c_uint64)]),
     ("rh_debug_batch_timing", C.c_int, [C.c_int]),
     ("rh_debug_batch_kernel_us", C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
 ]

@@ -11,6 +11,9 @@ summed from the decoded columns, and a key that appears twice keeps its last ent
 sequential replay leaves.  PersistedState.members and .tombstone_acks, which follow the entries
 in the file, are host state; `decode_tail` reads them on the host.
 
+Entries whose lengths are in their own bytes -- String keys (RH_KEY_STR stores) and Vec<u8> /
+String values (VARBYTES) -- take the byte-granular locate: `ragged=True` (RH_FORM_RAGGED).
+
 Errors are the reference's: a short file, a wrong magic or format version, or entries that do
 not parse raise RsosHipError with code ERR_DATA (io::ErrorKind::InvalidData) -- never a
 silent fresh start (persistence.rs:111-114).
@@ -60,10 +63,22 @@ def read_header(data, length: Optional[int] = None) -> int:
     return int(out.value)
 
 
-def load_snapshot(data, dated=None, projection=None, key_form: str = "array") -> SnapshotInfo:
+def _form(key_form: str, ragged: bool) -> int:
+    return _FORMS[key_form] | (A.FORM_RAGGED if ragged else 0)
+
+
+def ragged_stats() -> Dict[str, int]:
+    """The calling thread's last ragged decode or reload (rh_debug_ragged_stats)."""
+    w = [C.c_uint64() for _ in range(4)]
+    A.check(A.lib().rh_debug_ragged_stats(*[C.byref(x) for x in w]), "rh_debug_ragged_stats")
+    return dict(zip(("segment_bytes", "segments", "rounds", "rewalked"), (int(x.value) for x in w)))
+
+
+def load_snapshot(data, dated=None, projection=None, key_form: str = "array", ragged: bool = False) -> SnapshotInfo:
     """Replace the contents of the dated and / or projection GpuFingerprintStore with the
     snapshot's entries.  `data`: the file's bytes on the host (bytes / bytearray / memoryview /
-    numpy), or a contiguous uint8 torch tensor already in HBM."""
+    numpy), or a contiguous uint8 torch tensor already in HBM.  `ragged`: the byte-granular
+    locate, which string-keyed stores (key_form "vec") and VARBYTES stores need."""
     if dated is None and projection is None:
         raise ValueError("no store given")
     info = A.SnapshotInfo()
@@ -80,15 +95,17 @@ def load_snapshot(data, dated=None, projection=None, key_form: str = "array") ->
         stream = torch.cuda.current_stream(data.device).cuda_stream
     A.check(A.lib().rh_store_load_snapshot(dated._h if dated is not None else None,
                                            projection._h if projection is not None else None,
-                                           _FORMS[key_form], ptr, size, 1 if is_dev else 0, C.byref(info), stream),
+                                           _form(key_form, ragged), ptr, size, 1 if is_dev else 0, C.byref(info),
+                                           stream),
             "rh_store_load_snapshot")
     del keep
     return SnapshotInfo.from_c(info)
 
 
-def decode_entries_device(schema: RecordSchema, data, key_form: str = "array"):
+def decode_entries_device(schema: RecordSchema, data, key_form: str = "array", ragged: bool = False):
     """Decode a device-resident snapshot's entries into device columns (keys, phys, logical,
-    node, tags, values); returns (columns, SnapshotInfo)."""
+    node, tags, values); returns (columns, SnapshotInfo).  With a VARBYTES schema (`ragged` only)
+    `values` is (heap, offsets): the values packed in file order, a tombstone's span empty."""
     import torch
     if not (data.is_cuda and data.is_contiguous() and data.dtype == torch.uint8):
         raise ValueError("data must be a contiguous uint8 device tensor")
@@ -104,10 +121,19 @@ def decode_entries_device(schema: RecordSchema, data, key_form: str = "array"):
     }
     c = A.Columns(*[cols[k].data_ptr() if cols[k].numel() else None
                     for k in ("keys", "phys", "logical", "node", "tags", "values")])
+    var = None
+    if ragged and schema.value_kind == A.VAL_VARBYTES:
+        # the values cannot take more bytes than the file has
+        heap = torch.empty((data.numel() + 3) // 4 * 4, dtype=torch.uint8, device=dev)
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        var = A.VarValues(heap.data_ptr(), offsets.data_ptr(), heap.numel())
+        c.values = C.addressof(var)
     s, info = schema.with_kind(A.REC_DATED).c(), A.SnapshotInfo()
     stream = torch.cuda.current_stream(dev).cuda_stream
-    A.check(A.lib().rh_snapshot_decode_device(C.byref(s), _FORMS[key_form], data.data_ptr(), data.numel(),
+    A.check(A.lib().rh_snapshot_decode_device(C.byref(s), _form(key_form, ragged), data.data_ptr(), data.numel(),
                                               C.byref(c), n, C.byref(info), stream), "rh_snapshot_decode_device")
+    if var is not None:
+        cols["values"] = (heap[:int(offsets[n])], offsets)
     return cols, SnapshotInfo.from_c(info)
 
 
@@ -134,17 +160,28 @@ class _Rd:
         return ipaddress.ip_address(self.take(4 if tag == 0 else 16))
 
 
-def decode_tail(data, entries_end: int, schema: RecordSchema, key_form: str = "array"
+def decode_tail(data, entries_end: int, schema: RecordSchema, key_form: str = "array", ragged: bool = False
                 ) -> Tuple[List, Dict[bytes, Dict[object, int]]]:
     """PersistedState.members (HashSet<IpAddr>) and .tombstone_acks (HashMap<K, HashMap<IpAddr,
-    u64>>), bincode fixint, starting at entries_end.  Keys are returned as their column bytes."""
+    u64>>), bincode fixint, starting at entries_end.  Keys are returned as their column bytes:
+    with `ragged` and a string-key schema, an ack key is read as u64 L + L bytes and returned as
+    its padded row (strkeys.pack_str_keys); L past the row's width - 1 is ERR_DATA."""
+    from .strkeys import pack_str_keys
     r = _Rd(bytes(data), entries_end)
     members = [r.ip() for _ in range(r.u64())]
     acks: Dict[bytes, Dict[object, int]] = {}
+    str_keys = ragged and schema.key_kind == A.KEY_STR
     for _ in range(r.u64()):
-        if key_form == "vec" and r.u64() != schema.key_row:
-            raise A.RsosHipError(A.ERR_DATA, "decode_tail", "ack key length differs from the schema's")
-        k = r.take(schema.key_row)
+        if str_keys:
+            L = r.u64()
+            if L >= schema.key_row:
+                raise A.RsosHipError(A.ERR_DATA, "decode_tail",
+                                     f"ack key length {L} does not fit a string key row of width {schema.key_row}")
+            k = pack_str_keys([r.take(L)], schema.key_row)[0].tobytes()
+        else:
+            if key_form == "vec" and r.u64() != schema.key_row:
+                raise A.RsosHipError(A.ERR_DATA, "decode_tail", "ack key length differs from the schema's")
+            k = r.take(schema.key_row)
         peers = {}
         for _ in range(r.u64()):
             ip = r.ip()

@@ -119,6 +119,9 @@ pub const RH_ERR_STATE: c_int = -5;
 pub const RH_ERR_DATA: c_int = -6;
 pub const RH_FORM_ARRAY: c_int = 0;
 pub const RH_FORM_VEC: c_int = 1;
+/// Flag OR-ed with `RH_FORM_ARRAY` / `RH_FORM_VEC`: the byte-granular snapshot locate, which
+/// `RH_KEY_STR` stores (`RH_FORM_VEC | RH_FORM_RAGGED`) and `RH_VAL_VARBYTES` schemas need.
+pub const RH_FORM_RAGGED: c_int = 2;
 
 // Every entry point of include/rsos_hip.h, in header order.
 extern "C" {
@@ -252,6 +255,8 @@ extern "C" {
     pub fn rh_debug_fail_point(name: *const c_char) -> c_int;
     pub fn rh_debug_reload_timing(on: c_int) -> c_int;
     pub fn rh_debug_last_reload_us(locate_us: *mut f64, lift_us: *mut f64) -> c_int;
+    pub fn rh_debug_ragged_stats(segment_bytes: *mut u64, segments: *mut u64, rounds: *mut u64,
+                                 rewalked: *mut u64) -> c_int;
     pub fn rh_debug_batch_timing(on: c_int) -> c_int;
     pub fn rh_debug_batch_kernel_us(lift_search_us: *mut f64, launches: *mut u64) -> c_int;
 }
