@@ -469,7 +469,12 @@ int rh_store_stats(rh_store *store, uint64_t *base_rows, uint64_t *delta_rows, u
  * Env RSOS_HIP_SMALL_MAX=<rows> (read when a store is created) caps the small path; 0 turns it off. */
 int rh_store_batch_stats(rh_store *store, uint64_t *small_batches, uint64_t *large_batches);
 
-/* ---- snapshot reload ------------------------------------------------------------------
+/* ---- snapshot reload and save ---------------------------------------------------------
+ * Both directions of the reference's persistence port (Persistence::load / ::save,
+ * lww-register/src/persistence.rs:132-137): rh_snapshot_decode_device and rh_store_load_snapshot
+ * read a file's entries on the device, rh_snapshot_encode_device (below, after them) writes them
+ * from device columns -- the bytes FileSnapshot::save (src/snapshot.rs:164-189) puts in front of
+ * PersistedState.members.  The file format is one; what follows describes it from the reader's side.
  * FileSnapshot (src/snapshot.rs:30-58): "RCNL", u32 LE format version 1, then bincode 1.3.3
  * (fixint, LE) of PersistedState<K, V> (lww-register/src/persistence.rs:62-70), whose first
  * field is entries: Vec<(K, Entry<Timestamp, V>)> (:32).  Reload replays the entries through
@@ -532,6 +537,45 @@ int rh_snapshot_decode_device(const rh_schema *schema, int key_form, const void 
  * info (nullable) reports what was read.                                                   */
 int rh_store_load_snapshot(rh_store *dated, rh_store *projection, int key_form, const void *bytes, size_t len,
                            int bytes_on_device, rh_snapshot_info *info, void *after_stream);
+/* Save: encode n dated records held in DEVICE columns as the head of an RCNL v1 snapshot:
+ * "RCNL", u32 LE 1, u64 LE n, then the n entries in row order (bincode 1.3.3 fixint, LE) -- what
+ * FileSnapshot::save writes before PersistedState.members, and what snapshot_inner
+ * (src/replicated_map/persistence.rs:155-187) hands it periodically and at shutdown.  The inverse of
+ * rh_snapshot_decode_device: the output reloads through either route.
+ * Schema: record_kind must be RH_REC_DATED (RH_ERR_ARG otherwise); every schema for which
+ * rh_schema_supported returns 1 is taken, one that returns 0 is RH_ERR_UNSUPPORTED, a bad one
+ * RH_ERR_ARG.
+ * key_form: outside 0..3 is RH_ERR_ARG "bad key_form".  The RH_FORM_RAGGED bit is accepted and
+ * changes no output byte.  RH_KEY_STR needs RH_FORM_VEC (RH_FORM_ARRAY: RH_ERR_ARG); U32, U64 and
+ * UNIT keys ignore the form.
+ * An entry: the key -- UNIT nothing; U32 / U64 4 / 8 bytes LE; BYTES of width W the W raw bytes
+ * (RH_FORM_ARRAY) or u64 W then the bytes (RH_FORM_VEC); STR in a row of width W u64 L then the
+ * row's first L bytes, L = min(row[W - 1], W - 1), the clip the lift applies -- then the stamp
+ * (phys u64, logical u32, node u64), the State variant as a u32 (0 where the tag is 0, 1 otherwise)
+ * and, only when the variant is 0, the value: UNIT nothing; U32 / U64 LE bytes; BYTES u64
+ * value_len then the row; VARBYTES u64 M then the M bytes at bytes[offsets[i] .. offsets[i + 1]).
+ * Columns: phys, logical and node non-NULL when n > 0; tags NULL = all present; keys and values
+ * as rh_lift_records_async takes device columns (16-byte aligned; VARBYTES: values points to a
+ * HOST rh_var_values holding device pointers, under the _device / _async contract stated there).
+ * Output: dev_out 16-byte aligned, cap bytes writable.  info is required (RH_ERR_ARG) and gets
+ * entries = n, tombstones = the number of nonzero tags, entries_end = the total length (16 + the
+ * entries; the caller appends PersistedState.members at that offset) and keys = n (nothing is
+ * deduplicated).  dev_out == NULL: only the length is computed (rh_wire_encode_range_aggregates'
+ * convention).  cap < entries_end: RH_ERR_ARG, nothing is written, and info is still filled, so the
+ * caller can size a buffer.  No byte at or past dev_out + entries_end is ever written.
+ * Malformed device columns -- a length byte above W - 1, nonzero padding, offsets that decrease or
+ * exceed bytes_len, tags other than 0 / 1 -- are a caller error that gives a wrong but well-formed
+ * file, never an out-of-range access: the length pass and the write pass clip every entry the same
+ * way (a decreasing span or one that starts past bytes_len is empty, one that ends past it is cut
+ * there), so the output always parses as n entries ending at entries_end.
+ * n >= 2^31 is RH_ERR_ARG; the total may exceed 2^32 (offsets are 64-bit).  n == 0 answers 16
+ * bytes without reading any column (cols may be NULL), and with dev_out == NULL without a device
+ * call.  Every argument check comes before any device call.
+ * Runs on `stream` and is synchronous on it (one read-back: the total and the tombstone count).
+ * Device memory: 16 B per entry of per-device scratch kept between calls, shared with
+ * rh_snapshot_decode_device (calls on one device take turns).                                */
+int rh_snapshot_encode_device(const rh_schema *schema, int key_form, const rh_columns *dev_cols, size_t n,
+                              void *dev_out, size_t cap, rh_snapshot_info *info, void *stream);
 
 /* ---- RangeAggregate wire codec ---------------------------------------------------------
  * RangeAggregate<K> (rbsr/src/protocol.rs:63-88) under the gossip codec: bincode 1.3.3

@@ -31,6 +31,7 @@
 #include "host_tier.hpp"
 #include "lift_kernels.hpp"
 #include "small_batch.hpp"
+#include "snap_encode.hpp"
 #include "snap_ragged.hpp"
 #include "snapshot_kernels.hpp"
 #include "store_kernels.hpp"
@@ -4549,6 +4550,18 @@ int snapshot_reload_ragged(rh_store *dated, rh_store *proj, int form, const void
     return RH_OK;
 }
 
+// The scratch of rh_snapshot_decode_device and rh_snapshot_encode_device: one per device, kept
+// between calls and held under the lock for a whole call (both are synchronous).  The decode's
+// tables are slots 100-108, the encode's 110-113.
+struct SnapScratch {
+    std::mutex mu;
+    std::vector<rh::Scratch> by_dev;
+};
+SnapScratch &snap_scratch() {
+    static SnapScratch s;
+    return s;
+}
+
 }  // namespace
 
 extern "C" {
@@ -4597,13 +4610,12 @@ int rh_snapshot_decode_device(const rh_schema *schema, int key_form, const void 
         return fail(RH_ERR_ARG, "device columns must be 16-byte aligned");
     // the decode tables are kept per device between calls (the call is synchronous, so the
     // next call may reuse them on any stream)
-    static std::mutex scr_mu;
-    static std::vector<rh::Scratch> scr_by_dev;
     int dev = 0;
     RH_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> g(scr_mu);
-    if ((int)scr_by_dev.size() <= dev) scr_by_dev.resize(dev + 1);
-    rh::Scratch &scr = scr_by_dev[dev];
+    SnapScratch &ss = snap_scratch();
+    std::lock_guard<std::mutex> g(ss.mu);
+    if ((int)ss.by_dev.size() <= dev) ss.by_dev.resize(dev + 1);
+    rh::Scratch &scr = ss.by_dev[dev];
     scr.stream = st;
     scr.err = hipSuccess;
     rh_snapshot_info inf{};
@@ -4616,6 +4628,82 @@ int rh_snapshot_decode_device(const rh_schema *schema, int key_form, const void 
     }
     if (!rc && info) *info = inf;
     return rc;
+}
+
+int rh_snapshot_encode_device(const rh_schema *schema, int key_form, const rh_columns *cols, size_t n, void *dev_out,
+                              size_t cap, rh_snapshot_info *info, void *stream) {
+    int rc = check_schema(schema);
+    if (rc) return rc;
+    const rh_schema &s = *schema;
+    if (s.record_kind != RH_REC_DATED)
+        return fail(RH_ERR_ARG, "snapshot encode needs record_kind DATED (the file holds (K, Entry<Timestamp, V>))");
+    if (key_form < 0 || key_form > 3) return fail(RH_ERR_ARG, "bad key_form");
+    const int form = key_form & 1;  // RH_FORM_RAGGED changes no output byte
+    if (is_str(s) && form != RH_FORM_VEC)
+        return fail(RH_ERR_ARG, "RH_KEY_STR keys are Vec / String keys in the file (u64 length, then the bytes): "
+                                "RH_FORM_VEC");
+    if (rh_schema_supported(schema) != 1)
+        return fail(RH_ERR_UNSUPPORTED, is_str(s) ? STR_VALUE_KINDS
+                                                  : "no specialised kernel for this schema: serialise on the host");
+    if (!info) return fail(RH_ERR_ARG, "info is NULL");
+    if (n >= (1ull << 31)) return fail(RH_ERR_ARG, "snapshot encode takes fewer than 2^31 entries");
+    if (!aligned16(dev_out)) return fail(RH_ERR_ARG, "dev_out must be 16-byte aligned");
+    if (n && (rc = check_cols(s, cols, n))) return rc;
+    rh_snapshot_info inf{};
+    inf.entries = n;
+    inf.keys = n;
+    inf.entries_end = 16;
+    if (n == 0 && !dev_out) {
+        *info = inf;
+        return RH_OK;
+    }
+    rh::RagFmt f;
+    f.key_mode = is_str(s) ? rh::RagFmt::KEY_STR
+                 : form == RH_FORM_VEC && s.key_kind == RH_KEY_BYTES ? rh::RagFmt::KEY_VEC : rh::RagFmt::KEY_RAW;
+    f.key_len = (uint32_t)key_row(s);
+    f.val_mode = is_var(s) ? rh::RagFmt::VAL_VAR : s.value_kind == RH_VAL_BYTES ? rh::RagFmt::VAL_VEC : rh::RagFmt::VAL_RAW;
+    f.val_len = (uint32_t)value_row(s);
+    rh::EncCols c;
+    if (n) {
+        c.keys = static_cast<const uint8_t *>(cols->keys);
+        c.phys = cols->phys;
+        c.logical = cols->logical;
+        c.node = cols->node;
+        c.tags = cols->tags;
+        if (is_var(s)) {
+            const rh_var_values *v = var_of(*cols);
+            c.values = v->bytes;
+            c.voffs = v->offsets;
+            c.vlimit = v->bytes_len;
+        } else {
+            c.values = static_cast<const uint8_t *>(cols->values);
+            c.vlimit = (uint64_t)n * f.val_len;
+        }
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int dev = 0;
+    RH_HIP(hipGetDevice(&dev));
+    SnapScratch &ss = snap_scratch();
+    std::lock_guard<std::mutex> g(ss.mu);
+    if ((int)ss.by_dev.size() <= dev) ss.by_dev.resize(dev + 1);
+    rh::Scratch &scr = ss.by_dev[dev];
+    scr.stream = st;
+    scr.err = hipSuccess;
+    if (n) {
+        rh::EncSizes sz;
+        RH_HIP(rh::encode_measure(f, c, n, scr, st, &sz));
+        if (scr.err) return fail(RH_ERR_OOM, "scratch allocation failed");
+        inf.tombstones = sz.tombstones;
+        inf.entries_end = 16 + sz.entry_bytes;
+    }
+    *info = inf;
+    if (!dev_out) return RH_OK;
+    if (cap < inf.entries_end)
+        return fail(RH_ERR_ARG, "the snapshot takes " + std::to_string(inf.entries_end) + " bytes, more than cap " +
+                                    std::to_string(cap) + " (nothing written)");
+    RH_HIP(rh::encode_write(f, c, n, static_cast<uint8_t *>(dev_out), scr, st));
+    RH_HIP(hipStreamSynchronize(st));
+    return RH_OK;
 }
 
 int rh_store_load_snapshot(rh_store *dated, rh_store *proj, int key_form, const void *bytes, size_t len,

@@ -117,6 +117,8 @@ SIGNATURES = [
     ("rh_snapshot_decode_device", C.c_int, [C.POINTER(Schema), C.c_int, VP, SZ, C.POINTER(Columns), SZ,
                                             C.POINTER(SnapshotInfo), VP]),
     ("rh_store_load_snapshot", C.c_int, [P, P, C.c_int, VP, SZ, C.c_int, C.POINTER(SnapshotInfo), VP]),
+    ("rh_snapshot_encode_device", C.c_int, [C.POINTER(Schema), C.c_int, C.POINTER(Columns), SZ, VP, SZ,
+                                            C.POINTER(SnapshotInfo), VP]),
     ("rh_wire_encode_range_aggregates", C.c_int, [C.POINTER(Schema), C.c_int, C.c_int, U8P, VP, U8P, VP, P, SZ,
                                                   U8P, SZ, C.POINTER(C.c_size_t)]),
     ("rh_wire_decode_range_aggregates", C.c_int, [C.POINTER(Schema), C.c_int, C.c_int, U8P, SZ, SZ, U8P, VP, U8P,

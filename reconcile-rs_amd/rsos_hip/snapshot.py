@@ -1,4 +1,4 @@
-"""Snapshot reload onto the GPU.
+"""Snapshot reload onto the GPU, and snapshot save from it.
 
 The load side of FileSnapshot (src/snapshot.rs:30-98) and the replay that follows it in
 ReplicatedMap::with_persistence (src/replicated_map/persistence.rs:108-143): every entry of
@@ -14,6 +14,12 @@ in the file, are host state; `decode_tail` reads them on the host.
 Entries whose lengths are in their own bytes -- String keys (RH_KEY_STR stores) and Vec<u8> /
 String values (VARBYTES) -- take the byte-granular locate: `ragged=True` (RH_FORM_RAGGED).
 
+The save side (FileSnapshot::save, src/snapshot.rs:164-189, driven by snapshot_inner,
+src/replicated_map/persistence.rs:155-187): `encode_entries_device` turns device columns into the
+file's header and entries on the GPU (rh_snapshot_encode_device), `encode_tail` is `decode_tail`'s
+inverse on the host, and `save_snapshot` writes the file the way the reference does (a sibling
+temporary file, fsync, rename, fsync of the directory).
+
 Errors are the reference's: a short file, a wrong magic or format version, or entries that do
 not parse raise RsosHipError with code ERR_DATA (io::ErrorKind::InvalidData) -- never a
 silent fresh start (persistence.rs:111-114).
@@ -22,6 +28,7 @@ from __future__ import annotations
 
 import ctypes as C
 import ipaddress
+import os
 import struct
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
@@ -188,3 +195,126 @@ def decode_tail(data, entries_end: int, schema: RecordSchema, key_form: str = "a
             peers[ip] = r.u64()
         acks[k] = peers
     return members, acks
+
+
+# ---- save: device columns -> the file ------------------------------------------------------------
+def _ip_bytes(a) -> bytes:
+    a = ipaddress.ip_address(a)
+    return struct.pack("<I", 0 if a.version == 4 else 1) + a.packed
+
+
+def _encode_columns(schema: RecordSchema, cols):
+    """(rh_columns, n, heap bytes, what must stay alive) of decode_entries_device's dict."""
+    import torch
+    n = int(cols["phys"].numel())
+    held = []
+
+    def ptr(t, nbytes, name):
+        if t is None or nbytes == 0:
+            return None
+        if not (t.is_cuda and t.is_contiguous()):
+            raise ValueError(f"column {name!r} must be a contiguous device tensor")
+        if t.numel() * t.element_size() != nbytes:
+            raise ValueError(f"column {name!r} has {t.numel() * t.element_size()} bytes, expected {nbytes}")
+        held.append(t)
+        return t.data_ptr()
+    c = A.Columns(ptr(cols.get("keys"), n * schema.key_row, "keys"), ptr(cols["phys"], n * 8, "phys"),
+                  ptr(cols["logical"], n * 4, "logical"), ptr(cols["node"], n * 8, "node"),
+                  ptr(cols.get("tags"), n, "tags"), None)
+    heap_bytes = 0
+    if schema.value_kind == A.VAL_VARBYTES:
+        heap, offs = cols["values"]
+        if not (heap.is_cuda and heap.is_contiguous() and heap.dtype == torch.uint8 and heap.dim() == 1):
+            raise ValueError("the value heap must be a contiguous 1-D uint8 device tensor")
+        if not (offs.is_cuda and offs.is_contiguous() and offs.element_size() == 8 and offs.numel() == n + 1):
+            raise ValueError("the value offsets must be n + 1 contiguous int64 / uint64 device entries")
+        heap_bytes = heap.numel()
+        if heap.numel() % 4 or heap.data_ptr() % 4:  # the kernels read whole words: pad a copy
+            heap = torch.cat([heap, torch.zeros(-heap.numel() % 4, dtype=torch.uint8, device=heap.device)])
+        var = A.VarValues(heap.data_ptr() if heap.numel() else None, offs.data_ptr(), heap.numel())
+        held += [heap, offs, var]
+        c.values = C.addressof(var)
+    else:
+        c.values = ptr(cols.get("values"), n * schema.value_row, "values")
+    return c, n, heap_bytes, held
+
+
+def encode_entries_device(schema: RecordSchema, cols, key_form: str = "array"):
+    """The inverse of decode_entries_device: `cols` (its dict -- keys, phys, logical, node, tags or
+    None, values; a VARBYTES schema's values are (heap, offsets)) encoded on the GPU as the file's
+    header and entries.  Returns (uint8 device tensor of entries_end bytes, SnapshotInfo); the
+    caller appends `encode_tail` at entries_end.  Runs on the tensors' current stream."""
+    import torch
+    c, n, heap_bytes, held = _encode_columns(schema, cols)
+    dev = cols["phys"].device
+    kpre = 8 if schema.key_kind == A.KEY_STR or (key_form == "vec" and schema.key_kind == A.KEY_BYTES) else 0
+    vpre = 8 if schema.value_kind in (A.VAL_BYTES, A.VAL_VARBYTES) else 0
+    bound = 16 + n * (kpre + schema.key_row + 24 + vpre + schema.value_row) + heap_bytes
+    out = torch.empty(bound, dtype=torch.uint8, device=dev)
+    s, info = schema.with_kind(A.REC_DATED).c(), A.SnapshotInfo()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    A.check(A.lib().rh_snapshot_encode_device(C.byref(s), _FORMS[key_form], C.byref(c), n, out.data_ptr(), bound,
+                                              C.byref(info), stream), "rh_snapshot_encode_device")
+    del held
+    return out[:int(info.entries_end)], SnapshotInfo.from_c(info)
+
+
+def encode_tail(members, acks, schema: RecordSchema, key_form: str = "array", ragged: bool = False) -> bytes:
+    """decode_tail's inverse: PersistedState.members and .tombstone_acks as the bytes that follow
+    the entries.  Ack keys are column rows (what decode_tail returns); a string-key row is written
+    as u64 L and its first L bytes, a byte key under key_form 'vec' as u64 width and the row."""
+    if key_form not in _FORMS:
+        raise ValueError(f"unknown key_form {key_form!r}")
+    out = [struct.pack("<Q", len(members))] + [_ip_bytes(m) for m in members]
+    acks = acks or {}
+    out.append(struct.pack("<Q", len(acks)))
+    W = schema.key_row
+    for row, peers in acks.items():
+        row = bytes(row)
+        if len(row) != W:
+            raise ValueError(f"ack key row of {len(row)} bytes, the schema's rows have {W}")
+        if schema.key_kind == A.KEY_STR:
+            L = row[W - 1]
+            if L > W - 1:
+                raise ValueError(f"ack key row has length byte {L} (at most {W - 1})")
+            out.append(struct.pack("<Q", L) + row[:L])
+        else:
+            out.append((struct.pack("<Q", W) if key_form == "vec" else b"") + row)
+        out.append(struct.pack("<Q", len(peers)))
+        out += [_ip_bytes(a) + struct.pack("<Q", int(ver)) for a, ver in peers.items()]
+    return b"".join(out)
+
+
+def write_snapshot_file(path, *parts) -> None:
+    """FileSnapshot::save's file sequence (src/snapshot.rs:164-189), host only: the parts written
+    to the sibling `path + ".tmp"`, flushed and fsynced, renamed over `path`, and the directory
+    fsynced (best effort: some file systems cannot sync a directory)."""
+    path = os.fspath(path)
+    tmp = path + ".tmp"
+    with open(tmp, "wb") as f:
+        for p in parts:
+            f.write(p)
+        f.flush()
+        os.fsync(f.fileno())
+    os.replace(tmp, path)
+    parent = os.path.dirname(path)
+    if parent:
+        try:
+            fd = os.open(parent, os.O_RDONLY)
+        except OSError:
+            return
+        try:
+            os.fsync(fd)
+        except OSError:
+            pass
+        finally:
+            os.close(fd)
+
+
+def save_snapshot(path, schema: RecordSchema, cols, members=(), acks=None, key_form: str = "array") -> SnapshotInfo:
+    """FileSnapshot::save for a map whose columns are in HBM: the entries encoded on the device
+    (encode_entries_device), copied to the host, the tail appended (encode_tail), the file replaced
+    atomically (write_snapshot_file)."""
+    head, info = encode_entries_device(schema, cols, key_form)
+    write_snapshot_file(path, head.cpu().numpy().tobytes(), encode_tail(list(members), acks, schema, key_form))
+    return info

@@ -201,6 +201,9 @@ extern "C" {
     pub fn rh_store_load_snapshot(dated: *mut rh_store, projection: *mut rh_store, key_form: c_int,
                                   bytes: *const c_void, len: usize, bytes_on_device: c_int,
                                   info: *mut rh_snapshot_info, after_stream: *mut c_void) -> c_int;
+    pub fn rh_snapshot_encode_device(schema: *const rh_schema, key_form: c_int, dev_cols: *const rh_columns, n: usize,
+                                     dev_out: *mut c_void, cap: usize, info: *mut rh_snapshot_info,
+                                     stream: *mut c_void) -> c_int;
     pub fn rh_wire_encode_range_aggregates(schema: *const rh_schema, key_form: c_int, msg_tag: c_int,
                                            start_kinds: *const u8, start_keys: *const c_void, end_kinds: *const u8,
                                            end_keys: *const c_void, aggregates: *const rh_aggregate, r: usize,
