@@ -650,9 +650,18 @@ int rh_estore_set_host_tier(rh_estore *store, int enable);
  * Splitters: until the first load the key space is cut evenly (u32 / u64 keys at multiples of
  * 2^32 / n and 2^64 / n, byte keys by their leading 8 bytes), so single inserts spread over the
  * shards; a load cuts its rows at equal counts (shard s gets rows [n_rows * s / n, n_rows * (s + 1) / n)).
+ * A load of DEVICE columns (rh_sstore_load_device, rh_sstore_load_snapshot) rounds every cut down to a
+ * multiple of 16 rows: shard s gets rows [c(s), c(s + 1)), c(s) = floor(n_rows * s / n) & ~15, c(n) =
+ * n_rows -- each shard's columns then start 16-byte aligned inside the caller's and are read in place.
  * apply: a batch with a repeated key is rejected (RH_ERR_ARG) before any shard changes.
+ * A DEVICE batch (rh_sstore_apply_device) differs: its keys are first seen by the shards' own sorts, so a
+ * repeated key -- equal keys always land in one shard -- is refused by that shard (RH_ERR_ARG, that
+ * shard unchanged) while other shards may have committed their rows; the map is then broken (every call
+ * but a load and destroy is RH_ERR_STATE) until the next load, as after any partial apply.  A batch
+ * whose rows all fall in one shard leaves the map whole.
  * Round outputs belong to the sharded store (valid until its next call), as rh_store_protocol_round's.
- * reserve: each shard reserves rows / n (+ 1/8) resident rows and batches of batch_rows.        */
+ * reserve: each shard reserves rows / n (+ 1/8) resident rows and batches of batch_rows; a device
+ * batch's routed copy gets room for batch_rows rows too.                                         */
 typedef struct rh_sstore rh_sstore;
 int rh_sstore_create(const int *devices, int n, const rh_schema *schema, rh_sstore **out);
 int rh_sstore_destroy(rh_sstore *store);
@@ -667,6 +676,57 @@ int rh_sstore_load(rh_sstore *store, const rh_columns *host_cols, size_t n);
 int rh_sstore_stage(rh_sstore *store, const rh_columns *host_cols, const uint8_t *ops, size_t m);
 int rh_sstore_apply(rh_sstore *store, const rh_columns *host_cols, const uint8_t *ops, size_t n, uint64_t *n_new,
                     uint64_t *n_overwritten, uint64_t *n_deleted);
+/* Device columns (the write side of rh_store_load_device / rh_store_apply_device, for a map over
+ * several shards).  `device` is the device the columns live on; they were written on `after_stream`, a
+ * stream of that device (NULL = its null stream).  A shard on `device` reads its rows in place; a
+ * shard elsewhere gets them by a device-to-device copy into columns the sharded store keeps on the
+ * shard's device, ordered by an event before its store reads them.  RH_KEY_STR key rows are not
+ * validated (as for rh_store_apply_device: a malformed row is a wrong fingerprint).
+ * load_device: keys sorted and strictly increasing, as for rh_store_load_device (each shard checks its
+ * own rows, the order across each cut is checked too; RH_ERR_ARG otherwise); cuts at multiples of 16
+ * rows (above); the splitters become the keys at the cuts.  A failed load leaves the map empty with
+ * even splitters, exactly as rh_sstore_load does; n = 0 empties it.  n >= 2^31 * 64 is refused on the
+ * arguments alone, a cut of 2^31 rows or more before any shard changes (RH_ERR_ARG, "Row cap").
+ * apply_device: dev_ops NULL = all inserts.  Takes the map's lock, applies staged rows first and refuses
+ * a broken map, as rh_sstore_apply does.  The batch is routed on `device` (rh_route_columns_device below)
+ * into columns the sharded store keeps between calls; with the per-shard counts in hand the row cap is
+ * checked for every shard before any shard changes; then every shard applies its segment
+ * (rh_store_apply_device) and the three counts are summed.  A repeated key: see "apply" above.
+ * n >= 2^32 is refused on the arguments alone (RH_ERR_ARG).                                     */
+int rh_sstore_load_device(rh_sstore *store, int device, const rh_columns *dev_cols, size_t n, void *after_stream);
+int rh_sstore_apply_device(rh_sstore *store, int device, const rh_columns *dev_cols, const uint8_t *dev_ops, size_t n,
+                           uint64_t *n_new, uint64_t *n_overwritten, uint64_t *n_deleted, void *after_stream);
+/* Snapshot reload into a sharded replica (rh_store_load_snapshot's counterpart; Persistence::load,
+ * lww-register/src/persistence.rs:132-137): the entries are decoded on `device`
+ * (rh_snapshot_decode_device: the flag-clear route, and RH_FORM_RAGGED for RH_KEY_STR keys with unit /
+ * u32 / u64 values) and loaded into each map from the same columns (rh_sstore_load_device; one lift per
+ * map).  Either map may be NULL; both must have the same shard count, the same devices and matching
+ * key and value kinds.  bytes_on_device: 0 = host bytes, 1 = bytes on `device`, complete before the call.
+ * The entries must be in strictly increasing key order -- what FileSnapshot::save (src/snapshot.rs:164-189)
+ * writes from the map's iteration; otherwise RH_ERR_UNSUPPORTED naming the first entry out of order,
+ * with both maps unchanged.  A corrupt file is RH_ERR_DATA before either map changes.  info (nullable) as
+ * rh_store_load_snapshot fills it, with keys = entries.  A failure while the maps load leaves both empty. */
+int rh_sstore_load_snapshot(rh_sstore *dated, rh_sstore *projection, int key_form, const void *bytes, size_t len,
+                            int bytes_on_device, int device, rh_snapshot_info *info);
+/* The partition rh_sstore_apply_device makes, on its own (for a map sharded over several processes):
+ * the n records of dev_in / dev_ops_in, on the current device, into `shards` (1..64) contiguous segments
+ * of dev_out / dev_ops_out.  Record i goes to shard s(i) = the number of splitters <= key[i]
+ * (host_splitters: shards - 1 keys, non-decreasing, in the key type's Ord: numeric for U32 / U64,
+ * memcmp for BYTES / STR rows of 8, 16, 32 or 64 bytes; other widths RH_ERR_UNSUPPORTED).  Stable: the
+ * rows of a shard keep their input order.  Shard s's rows are output rows [starts[s], starts[s] +
+ * counts[s]); every start is a multiple of 16 rows, so each column of a segment meets the 16-byte rule
+ * for device columns; the rows from a segment's end to the next multiple of 16 are zero-filled and
+ * counted nowhere.  Columns: keys, values (value_len > 0), phys / logical / node (DATED) are required
+ * in both; tags (DATED / PROJECTION) and ops are moved when given (then required in the output); an
+ * absent column stays absent.  Fixed-width values only (RH_VAL_VARBYTES: RH_ERR_UNSUPPORTED, the message
+ * names VARBYTES).  cap_rows: the rows each output column has room for; n + 16 * shards always suffices,
+ * less is RH_ERR_ARG with nothing written.  Nothing is read at or past row n, nothing written at or
+ * past row cap_rows.  counts / starts: host arrays of `shards` entries.  Every argument check comes
+ * before any device call; n = 0 makes none.  Runs on `stream`, synchronous on it (one read-back: the
+ * counts).  n >= 2^32: RH_ERR_ARG.                                                              */
+int rh_route_columns_device(const rh_schema *schema, const void *host_splitters, int shards, const rh_columns *dev_in,
+                            const uint8_t *dev_ops_in, size_t n, const rh_columns *dev_out, uint8_t *dev_ops_out,
+                            size_t cap_rows, uint64_t *counts, uint64_t *starts, void *stream);
 int rh_sstore_len(rh_sstore *store, uint64_t *out);
 int rh_sstore_aggregates(rh_sstore *store, const uint64_t *lo, const uint64_t *hi, size_t r, rh_aggregate *out);
 int rh_sstore_aggregate_keys(rh_sstore *store, int lo_kind, const void *lo_key, int hi_kind, const void *hi_key,

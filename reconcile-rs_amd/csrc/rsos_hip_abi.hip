@@ -413,6 +413,7 @@ struct DevBuf {
 namespace rh {
 int set_error(int code, const std::string &msg) { return fail(code, msg); }
 bool debug_fail_point(const char *name) { return fail_point(name); }
+int check_schema_arg(const rh_schema *s) { return check_schema(s); }
 int check_str_rows(const rh_schema &s, const void *keys, size_t n) {
     rh_columns h{};
     h.keys = keys;

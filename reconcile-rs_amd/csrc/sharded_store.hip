@@ -37,6 +37,7 @@
 #include "../../include/rsos_hip.h"
 #include "internal.hpp"
 #include "round_decide.hpp"
+#include "shard_route.hpp"
 
 namespace rh {
 int set_error(int code, const std::string &msg);  // rsos_hip_abi.hip: the calling thread's rh_last_error
@@ -200,6 +201,97 @@ int value_row(const rh_schema &s) {
     }
 }
 
+int hip_fail(hipError_t e, const char *what) {
+    return fail(e == hipErrorOutOfMemory ? RH_ERR_OOM : RH_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+#define SS_HIP(expr)                                      \
+    do {                                                  \
+        const hipError_t e_ = (expr);                     \
+        if (e_ != hipSuccess) return hip_fail(e_, #expr); \
+    } while (0)
+
+// Device columns the sharded store owns on one device, with a stream and an event of that device:
+// the routed rows of a device batch, a shard's rows copied from another device, a decoded snapshot.
+// Kept between calls and grown on demand (every call that uses them is synchronous).
+struct ColBuf {
+    enum { KEYS, PHYS, LOGICAL, NODE, TAGS, VALUES, OPS, NCOL };
+    int device = -1;
+    size_t cap = 0;  // rows
+    void *p[NCOL] = {};
+    size_t width[NCOL] = {};
+    hipStream_t st = nullptr;
+    hipEvent_t ev = nullptr;
+    int open(int dev) {
+        SS_HIP(hipSetDevice(dev));
+        if (st) return RH_OK;
+        device = dev;
+        SS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        SS_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        return RH_OK;
+    }
+    // room for `rows` rows of every column a DATED record of this key / value shape has, and ops
+    int ensure(int dev, const rh_schema &s, size_t rows) {
+        if (int rc = open(dev)) return rc;
+        if (rows <= cap) return RH_OK;
+        drop();
+        const size_t w[NCOL] = {(size_t)key_row(s), 8, 4, 8, 1, (size_t)value_row(s), 1};
+        for (int c = 0; c < NCOL; c++) {
+            width[c] = w[c];
+            if (w[c]) SS_HIP(hipMalloc(&p[c], rows * w[c] + 64));
+        }
+        cap = rows;
+        return RH_OK;
+    }
+    void *at(int c, size_t row) const { return p[c] ? static_cast<uint8_t *>(p[c]) + row * width[c] : nullptr; }
+    // every column from `row` on
+    rh_columns all(size_t row) const {
+        return rh_columns{at(KEYS, row),
+                          static_cast<const uint64_t *>(at(PHYS, row)),
+                          static_cast<const uint32_t *>(at(LOGICAL, row)),
+                          static_cast<const uint64_t *>(at(NODE, row)),
+                          static_cast<const uint8_t *>(at(TAGS, row)),
+                          at(VALUES, row)};
+    }
+    // ... those of them the caller's batch `like` has (a column it left out was never written here)
+    rh_columns cols(size_t row, const rh_columns &like) const {
+        rh_columns c = all(row);
+        if (!like.keys) c.keys = nullptr;
+        if (!like.phys) c.phys = nullptr;
+        if (!like.logical) c.logical = nullptr;
+        if (!like.node) c.node = nullptr;
+        if (!like.tags) c.tags = nullptr;
+        if (!like.values) c.values = nullptr;
+        return c;
+    }
+    void drop() {
+        for (int c = 0; c < NCOL; c++) {
+            if (p[c]) (void)hipFree(p[c]);
+            p[c] = nullptr;
+        }
+        cap = 0;
+    }
+    void release() {
+        if (device < 0) return;
+        (void)hipSetDevice(device);
+        drop();
+        if (st) (void)hipStreamDestroy(st);
+        if (ev) (void)hipEventDestroy(ev);
+        st = nullptr, ev = nullptr;
+    }
+};
+
+// the columns of `c` from row `a` on (columns the schema does not use, or the caller left out, stay NULL)
+rh_columns columns_from(const rh_schema &s, const rh_columns &c, size_t a) {
+    const bool dated = s.record_kind == RH_REC_DATED;
+    auto at = [&](const void *p, size_t w) -> const void * { return p ? static_cast<const uint8_t *>(p) + a * w : nullptr; };
+    return rh_columns{at(c.keys, (size_t)key_row(s)),
+                      static_cast<const uint64_t *>(dated ? at(c.phys, 8) : nullptr),
+                      static_cast<const uint32_t *>(dated ? at(c.logical, 4) : nullptr),
+                      static_cast<const uint64_t *>(dated ? at(c.node, 8) : nullptr),
+                      static_cast<const uint8_t *>(at(c.tags, 1)),
+                      at(c.values, (size_t)value_row(s))};
+}
+
 const rh_aggregate kZero{{0, 0, 0, 0}, 0};
 void agg_add(rh_aggregate &a, const rh_aggregate &b) {
     rh_fp_add(a.fingerprint, b.fingerprint, a.fingerprint);
@@ -245,6 +337,47 @@ struct rh_sstore {
     std::string broken;
     int health() const {
         return broken.empty() ? RH_OK : rh::set_error(RH_ERR_STATE, "sharded store: " + broken + "; load to recover");
+    }
+
+    // ---- device columns (rh_sstore_load_device / _apply_device / _load_snapshot) ----------------
+    // stage: per source device, a device batch routed into per-shard segments, or a snapshot's
+    // decoded entries; peer[t]: shard t's rows copied from another device.  batch_hint: rh_sstore_reserve's
+    // batch_rows, the least capacity a stage gets.
+    std::vector<std::unique_ptr<ColBuf>> stages;
+    std::vector<ColBuf> peer;
+    uint64_t batch_hint = 0;
+    ColBuf *stage_for(int device) {
+        for (auto &b : stages)
+            if (b->device == device) return b.get();
+        stages.emplace_back(new ColBuf());
+        stages.back()->device = device;
+        return stages.back().get();
+    }
+    void release_device_columns() {
+        for (auto &b : stages) b->release();
+        for (ColBuf &b : peer) b.release();
+        stages.clear();
+    }
+    // Shard t reads `rows` rows of `src` (on `device`, complete once src_ev has happened): in place
+    // when the shard lives there, else from peer[t] after a device-to-device copy on peer[t]'s
+    // stream, which the shard's store then waits for (*after).  ops (nullable) travels with them.
+    int shard_view(int t, int device, const rh_columns &src, const uint8_t *src_ops, size_t rows, hipEvent_t src_ev,
+                   void *src_stream, rh_columns *view, const uint8_t **ops, void **after) {
+        if (dev[t] == device) {
+            *view = src, *ops = src_ops, *after = src_stream;
+            return RH_OK;
+        }
+        ColBuf &b = peer[t];
+        if (int rc = b.ensure(dev[t], schema, rows)) return rc;
+        SS_HIP(hipStreamWaitEvent(b.st, src_ev, 0));
+        const void *from[ColBuf::NCOL] = {src.keys, src.phys, src.logical, src.node, src.tags, src.values, src_ops};
+        for (int c = 0; c < ColBuf::NCOL; c++)
+            if (from[c] && b.width[c])
+                SS_HIP(hipMemcpyPeerAsync(b.p[c], dev[t], from[c], device, rows * b.width[c], b.st));
+        *view = b.cols(0, src);
+        *ops = src_ops ? static_cast<const uint8_t *>(b.p[ColBuf::OPS]) : nullptr;
+        *after = b.st;
+        return RH_OK;
     }
 
     // ---- key order (the key type's Ord: numeric for u32 / u64 keys stored LE, bytewise else) ----
@@ -1107,6 +1240,7 @@ int rh_sstore_create(const int *devices, int n, const rh_schema *schema, rh_ssto
     s->off.assign(n + 1, 0);
     s->sizes_ok = true;
     s->dirty.assign(n, 0);
+    s->peer.resize(n);
     s->roots.assign(n, kZero);
     s->root_ok.assign(n, 0);
     s->even_splitters();
@@ -1125,6 +1259,7 @@ int rh_sstore_destroy(rh_sstore *s) {
     if (!s) return RH_OK;
     delete s->pool;
     for (rh_store *t : s->shards) rh_store_destroy(t);
+    s->release_device_columns();
     delete s;
     return RH_OK;
 }
@@ -1316,6 +1451,251 @@ int rh_sstore_apply(rh_sstore *s, const rh_columns *h, const uint8_t *ops, size_
     if (n_new) *n_new = tot[0];
     if (n_over) *n_over = tot[1];
     if (n_del) *n_del = tot[2];
+    return RH_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+const char *const kRowCap = "store size limit (2^31 rows) exceeded in one shard: use more shards";
+
+void empty_map(rh_sstore *s) {
+    const rh_columns none{};
+    for (int j = 0; j < s->G; j++) (void)rh_store_load(s->shards[j], &none, 0);
+    s->even_splitters();
+    s->sizes.assign(s->G, 0), s->off.assign(s->G + 1, 0), s->sizes_ok = true;
+}
+
+// rh_sstore_load_device under the map's lock (s->mu held; n < 2^31 * G checked by the caller)
+int load_device_locked(rh_sstore *s, int device, const rh_columns &cols, size_t n, void *after_stream) {
+    const int G = s->G;
+    const size_t kl = s->kl;
+    // equal counts, each cut rounded down to a multiple of 16 rows: a shard's columns then start
+    // 16-byte aligned inside the caller's, and shards on `device` read them in place
+    std::vector<uint64_t> cut(G + 1);
+    for (int j = 0; j < G; j++) cut[j] = (uint64_t)((unsigned __int128)n * (unsigned)j / (unsigned)G) & ~15ull;
+    cut[G] = n;
+    for (int j = 0; j < G; j++)
+        if (cut[j + 1] - cut[j] >= (1ull << 31)) return fail(RH_ERR_ARG, kRowCap);
+    const uint8_t *keys = static_cast<const uint8_t *>(cols.keys);
+    hipStream_t producer = static_cast<hipStream_t>(after_stream);
+    ColBuf *stg = s->stage_for(device);
+    s->changed();
+    s->broken.clear();
+    std::fill(s->dirty.begin(), s->dirty.end(), 0);
+    // edge[j]: the rows cut[j] - 1 and cut[j] (the second alone when cut[j] is 0)
+    std::vector<uint8_t> edge((size_t)G * 2 * kl + 1, 0);
+    auto run = [&]() -> int {
+        if (int rc = stg->open(device)) return rc;
+        SS_HIP(hipEventRecord(stg->ev, producer));  // the caller's columns are whole once this has happened
+        if (n && G > 1) {
+            SS_HIP(hipStreamWaitEvent(stg->st, stg->ev, 0));
+            for (int j = 1; j < G; j++) {
+                uint8_t *e = edge.data() + (size_t)j * 2 * kl;
+                if (cut[j]) SS_HIP(hipMemcpyAsync(e, keys + (cut[j] - 1) * kl, 2 * kl, hipMemcpyDeviceToHost, stg->st));
+                else SS_HIP(hipMemcpyAsync(e + kl, keys, kl, hipMemcpyDeviceToHost, stg->st));
+            }
+            SS_HIP(hipStreamSynchronize(stg->st));
+            // strictly increasing across the cuts too (each shard checks its own rows)
+            for (int j = 1; j < G; j++) {
+                const uint8_t *e = edge.data() + (size_t)j * 2 * kl;
+                if (cut[j] && s->cmp(e, e + kl) >= 0)
+                    return fail(RH_ERR_ARG, "keys must be strictly increasing (sorted, no duplicates)");
+            }
+        }
+        return s->each(s->all(), [&](int j) -> int {
+            const size_t rows = cut[j + 1] - cut[j];
+            if (!rows) {
+                const rh_columns none{};
+                return rh_store_load(s->shards[j], &none, 0);
+            }
+            rh_columns view;
+            const uint8_t *ops;
+            void *after;
+            if (int rc = s->shard_view(j, device, columns_from(s->schema, cols, cut[j]), nullptr, rows, stg->ev,
+                                       after_stream, &view, &ops, &after))
+                return rc;
+            return rh_store_load_device(s->shards[j], &view, rows, after);
+        });
+    };
+    if (int rc = run()) {  // the map is left empty with even splitters, as rh_sstore_load leaves it
+        const std::string msg = rh_last_error();
+        empty_map(s);
+        return fail(rc, msg);
+    }
+    if (n) {
+        s->split.resize((size_t)(G - 1) * kl);
+        for (int j = 1; j < G; j++) memcpy(s->split.data() + (j - 1) * kl, edge.data() + (size_t)j * 2 * kl + kl, kl);
+    } else {
+        s->even_splitters();
+    }
+    for (int j = 0; j < G; j++) s->sizes[j] = cut[j + 1] - cut[j];
+    for (int j = 0; j <= G; j++) s->off[j] = cut[j];
+    s->sizes_ok = true;
+    return RH_OK;
+}
+
+int check_device_columns(const rh_sstore *s, const rh_columns *c, size_t n) {
+    if (!n) return RH_OK;
+    const rh_schema &sc = s->schema;
+    if (s->kl && !c->keys) return fail(RH_ERR_ARG, "keys column is NULL");
+    if (sc.value_kind != RH_VAL_UNIT && !c->values) return fail(RH_ERR_ARG, "values column is NULL");
+    if (sc.record_kind == RH_REC_DATED && (!c->phys || !c->logical || !c->node))
+        return fail(RH_ERR_ARG, "DATED records need phys / logical / node columns");
+    return RH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rh_sstore_load_device(rh_sstore *s, int device, const rh_columns *dev_cols, size_t n, void *after_stream) {
+    // the row cap first: with at most 64 shards this many rows overflow one whatever the cuts
+    if (n >= (1ull << 31) * 64) return fail(RH_ERR_ARG, kRowCap);
+    if (!s || !dev_cols) return fail(RH_ERR_ARG, "NULL");
+    if (int rc = check_device_columns(s, dev_cols, n)) return rc;
+    std::lock_guard<std::mutex> g(s->mu);
+    return load_device_locked(s, device, *dev_cols, n, after_stream);
+}
+
+int rh_sstore_apply_device(rh_sstore *s, int device, const rh_columns *dev_cols, const uint8_t *dev_ops, size_t m,
+                           uint64_t *n_new, uint64_t *n_over, uint64_t *n_del, void *after_stream) {
+    // a batch this large overflows a shard of any map (2^31 rows each, RH_STORE_MAX_ROWS) or the route
+    if (m >= (1ull << 32)) return fail(RH_ERR_ARG, std::string(kRowCap) + " (a device batch holds fewer than 2^32 rows)");
+    if (!s || !dev_cols) return fail(RH_ERR_ARG, "NULL");
+    if (int rc = check_device_columns(s, dev_cols, m)) return rc;
+    std::unique_lock<std::mutex> g;
+    int rc = lock_sizes(s, g);  // staged rows first: they were staged before this batch
+    if (rc) return rc;
+    uint64_t tot[3] = {0, 0, 0};
+    if (m) {
+        const int G = s->G;
+        const rh_columns in = columns_from(s->schema, *dev_cols, 0);
+        ColBuf *stg = s->stage_for(device);
+        const size_t cap = std::max<uint64_t>(m, s->batch_hint) + rh::ROUTE_ALIGN * (size_t)G;
+        if ((rc = stg->ensure(device, s->schema, cap))) return rc;
+        SS_HIP(hipEventRecord(stg->ev, static_cast<hipStream_t>(after_stream)));
+        SS_HIP(hipStreamWaitEvent(stg->st, stg->ev, 0));
+        const rh_columns out = stg->cols(0, in);
+        uint8_t *ops_out = dev_ops ? static_cast<uint8_t *>(stg->p[ColBuf::OPS]) : nullptr;
+        uint64_t cnt[64], start[64];
+        if ((rc = rh_route_columns_device(&s->schema, s->split.data(), G, &in, dev_ops, m, &out, ops_out, stg->cap, cnt,
+                                          start, stg->st)))
+            return rc;
+        std::vector<int> idx;
+        for (int t = 0; t < G; t++) {
+            if (!cnt[t]) continue;
+            idx.push_back(t);
+            if (s->sizes[t] + cnt[t] >= (1ull << 31)) return fail(RH_ERR_ARG, kRowCap);  // every row counted as new
+        }
+        SS_HIP(hipEventRecord(stg->ev, stg->st));  // (the route has finished: it is synchronous)
+        s->changed();
+        uint64_t c[64][3] = {};
+        const bool inject = rh::debug_fail_point("sstore.apply_last_shard");
+        rc = s->each(idx, [&](int t) -> int {
+            if (inject && t == idx.back()) return rh::set_error(RH_ERR_OOM, "injected failure (sstore apply)");
+            rh_columns view;
+            const uint8_t *ops;
+            void *after;
+            if (int q = s->shard_view(t, device, stg->cols(start[t], in), ops_out ? ops_out + start[t] : nullptr, cnt[t],
+                                      stg->ev, stg->st, &view, &ops, &after))
+                return q;
+            return rh_store_apply_device(s->shards[t], &view, ops, cnt[t], &c[t][0], &c[t][1], &c[t][2], after);
+        });
+        if (rc) {
+            // a repeated key (seen only by its shard's sort: equal keys share a shard, which refuses
+            // them unchanged) or a device failure: with more than one shard written the others may
+            // have committed their part
+            if (idx.size() > 1) s->broken = "a device apply failed in one shard after others may have committed their rows";
+            return rc;
+        }
+        for (int t : idx)
+            for (int i = 0; i < 3; i++) tot[i] += c[t][i];
+    }
+    if (n_new) *n_new = tot[0];
+    if (n_over) *n_over = tot[1];
+    if (n_del) *n_del = tot[2];
+    return RH_OK;
+}
+
+int rh_sstore_load_snapshot(rh_sstore *dated, rh_sstore *proj, int key_form, const void *bytes, size_t len,
+                            int on_device, int device, rh_snapshot_info *info) {
+    if (!dated && !proj) return fail(RH_ERR_ARG, "no map given");
+    if (!bytes && len) return fail(RH_ERR_ARG, "bytes is NULL");
+    if (dated && dated->schema.record_kind != RH_REC_DATED) return fail(RH_ERR_ARG, "dated map must be DATED");
+    if (proj && proj->schema.record_kind != RH_REC_PROJECTION) return fail(RH_ERR_ARG, "projection map must be PROJECTION");
+    if (dated && proj) {
+        const rh_schema &a = dated->schema, &b = proj->schema;
+        if (a.key_kind != b.key_kind || a.key_len != b.key_len || a.value_kind != b.value_kind || a.value_len != b.value_len ||
+            dated->G != proj->G || dated->dev != proj->dev)
+            return fail(RH_ERR_ARG, "dated and projection maps differ in key / value kind, shard count or devices");
+    }
+    rh_sstore *a = dated ? dated : proj;
+    std::unique_lock<std::mutex> la(a->mu, std::defer_lock), lb;
+    if (dated && proj) {
+        lb = std::unique_lock<std::mutex>(proj->mu, std::defer_lock);
+        std::lock(la, lb);
+    } else {
+        la.lock();
+    }
+    // the header (host bytes; a device file's first 16 bytes are copied down)
+    ColBuf *stg = a->stage_for(device);
+    int rc;
+    if ((rc = stg->open(device))) return rc;
+    uint8_t h[16] = {0};
+    const size_t hl = std::min<size_t>(len, 16);
+    if (hl && on_device) SS_HIP(hipMemcpy(h, bytes, hl, hipMemcpyDeviceToHost));
+    else if (hl) memcpy(h, bytes, hl);
+    uint64_t n = 0;
+    if ((rc = rh_snapshot_header(h, len, &n))) return rc;
+    if (n >= (1ull << 31)) return fail(RH_ERR_DATA, "snapshot: 2^31 entries or more");
+    // the file on the device, and a word for the order check behind it
+    struct Tmp {
+        void *p = nullptr;
+        ~Tmp() {
+            if (p) (void)hipFree(p);
+        }
+    } tmp;
+    const size_t at_word = on_device ? 0 : (len + 15) & ~size_t(15);
+    SS_HIP(hipMalloc(&tmp.p, at_word + 16));
+    const void *dev_bytes = bytes;
+    if (!on_device) {
+        SS_HIP(hipMemcpyAsync(tmp.p, bytes, len, hipMemcpyHostToDevice, stg->st));
+        dev_bytes = tmp.p;
+    }
+    unsigned long long *first = reinterpret_cast<unsigned long long *>(static_cast<uint8_t *>(tmp.p) + at_word);
+    // the entries decoded into columns on `device`: nothing below changes a map until they are whole
+    rh_schema ds = a->schema;
+    ds.record_kind = RH_REC_DATED;
+    if ((rc = stg->ensure(device, ds, std::max<size_t>(n, 1)))) return rc;
+    const rh_columns cols = stg->all(0);
+    rh_snapshot_info inf{};
+    if ((rc = rh_snapshot_decode_device(&ds, key_form, dev_bytes, len, &cols, stg->cap, &inf, stg->st))) return rc;
+    // FileSnapshot::save writes the map's iteration, so the keys increase strictly; any other file
+    // would need the reload's sort and last-wins pass over all shards
+    const bool numeric = ds.key_kind == RH_KEY_U32 || ds.key_kind == RH_KEY_U64;
+    if (!rh::route_key_supported((uint32_t)a->kl, numeric))
+        return fail(RH_ERR_UNSUPPORTED, "sharded snapshot reload: keys must be u32, u64 or rows of 8, 16, 32 or 64 bytes");
+    SS_HIP(rh::launch_first_unsorted(static_cast<const uint8_t *>(cols.keys), (uint32_t)a->kl, numeric, n, first, stg->st));
+    unsigned long long bad = ~0ull;
+    SS_HIP(hipMemcpyAsync(&bad, first, 8, hipMemcpyDeviceToHost, stg->st));
+    SS_HIP(hipStreamSynchronize(stg->st));
+    if (bad != ~0ull)
+        return fail(RH_ERR_UNSUPPORTED, "sharded snapshot reload needs entries in strictly increasing key order: entry " +
+                                            std::to_string(bad) + " is not above entry " + std::to_string(bad - 1));
+    for (rh_sstore *x : {dated, proj}) {
+        if (!x) continue;
+        const rh_columns c = columns_from(x->schema, cols, 0);
+        if ((rc = load_device_locked(x, device, c, n, stg->st))) {
+            const std::string msg = rh_last_error();
+            for (rh_sstore *y : {dated, proj})  // never one map replaced beside the other's old contents
+                if (y) empty_map(y);
+            return fail(rc, msg);
+        }
+    }
+    inf.keys = inf.entries;
+    if (info) *info = inf;
     return RH_OK;
 }
 
@@ -1560,6 +1940,7 @@ int rh_sstore_reserve(rh_sstore *s, uint64_t rows, uint64_t batch_rows) {
     if (!s) return fail(RH_ERR_ARG, "sstore is NULL");
     std::lock_guard<std::mutex> g(s->mu);
     const uint64_t per = (rows + s->G - 1) / s->G;
+    s->batch_hint = batch_rows;  // a device batch's routed rows (rh_sstore_apply_device) get this much room at least
     return s->each(s->all(), [&](int t) -> int { return rh_store_reserve(s->shards[t], per + per / 8, batch_rows); });
 }
 

@@ -142,6 +142,12 @@ SIGNATURES = [
     ("rh_sstore_stage", C.c_int, [P, C.POINTER(Columns), U8P, SZ]),
     ("rh_sstore_apply", C.c_int, [P, C.POINTER(Columns), U8P, SZ, C.POINTER(C.c_uint64),
                                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("rh_sstore_load_device", C.c_int, [P, C.c_int, C.POINTER(Columns), SZ, VP]),
+    ("rh_sstore_apply_device", C.c_int, [P, C.c_int, C.POINTER(Columns), U8P, SZ, C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), VP]),
+    ("rh_sstore_load_snapshot", C.c_int, [P, P, C.c_int, VP, SZ, C.c_int, C.c_int, C.POINTER(SnapshotInfo)]),
+    ("rh_route_columns_device", C.c_int, [C.POINTER(Schema), VP, C.c_int, C.POINTER(Columns), U8P, SZ,
+                                          C.POINTER(Columns), U8P, SZ, U64P, U64P, VP]),
     ("rh_sstore_len", C.c_int, [P, C.POINTER(C.c_uint64)]),
     ("rh_sstore_aggregates", C.c_int, [P, U64P, U64P, SZ, P]),
     ("rh_sstore_aggregate_keys", C.c_int, [P, C.c_int, VP, C.c_int, VP, C.POINTER(Aggregate)]),

@@ -101,6 +101,37 @@ def _columns(cols: Dict[str, torch.Tensor]) -> A.Columns:
     return c
 
 
+def route_columns(schema: RecordSchema, splitters, shards: int, cols: Dict[str, torch.Tensor],
+                  ops: Optional[torch.Tensor] = None, out: Optional[Dict[str, torch.Tensor]] = None,
+                  ops_out: Optional[torch.Tensor] = None, cap_rows: Optional[int] = None):
+    """The sharded store's partition of a device batch, on its own (rh_route_columns_device): record
+    i goes to shard s = the number of `splitters` (shards - 1 key rows, uint8, non-decreasing) <= its
+    key; each shard's rows form one segment of the output columns, in input order, starting at a
+    multiple of 16 rows.  Returns (out columns, out ops, counts, starts): shard s's rows are
+    out[c][starts[s] : starts[s] + counts[s]].  `out` / `ops_out`: preallocated columns with room for
+    `cap_rows` rows (default: new ones of n + 16 * shards rows).  Synchronous on the current stream."""
+    import numpy as np
+    n = _check_cols(schema, cols)
+    if ops is not None and (ops.numel() != n or not ops.is_cuda):
+        raise ValueError("ops must be n device bytes")
+    dev = next(iter(cols.values())).device
+    if cap_rows is None:
+        cap_rows = n + 16 * max(shards, 0)
+    if out is None:
+        out = {k: torch.empty((cap_rows,) + tuple(v.shape[1:]), dtype=v.dtype, device=dev)
+               for k, v in cols.items() if v is not None}
+    if ops is not None and ops_out is None:
+        ops_out = torch.empty(cap_rows, dtype=torch.uint8, device=dev)
+    sp = np.ascontiguousarray(splitters, dtype=np.uint8).reshape(-1)
+    counts, starts = np.zeros(max(shards, 1), np.uint64), np.zeros(max(shards, 1), np.uint64)
+    s, cin, cout = schema.c(), _columns(cols), _columns(out)
+    A.check(A.lib().rh_route_columns_device(C.byref(s), sp.ctypes.data if sp.size else None, shards, C.byref(cin),
+                                            _ptr(ops), n, C.byref(cout), _ptr(ops_out), cap_rows,
+                                            counts.ctypes.data, starts.ctypes.data, _stream()),
+            "rh_route_columns_device")
+    return out, ops_out, counts[:shards], starts[:shards]
+
+
 def lift_records(schema: RecordSchema, cols: Dict[str, torch.Tensor], block_sums: bool = True,
                  fps: Optional[torch.Tensor] = None, bsums: Optional[torch.Tensor] = None
                  ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:

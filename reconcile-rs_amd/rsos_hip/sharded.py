@@ -13,6 +13,8 @@ no device-to-device traffic and one host thread per shard (include/rsos_hip.h, c
                         (Aggregate's Add, rsos/src/aggregate.rs:79-89)
   select(r)             the shard whose rank interval holds r
   apply / stage         rows routed to their key's shard by the splitters
+  load_bulk_device /    records already in HBM: a load cut at multiples of 16 rows and read in place,
+  apply_device          a batch partitioned by the splitters on the GPU (csrc/shard_route.hip)
   protocol round        a run of segments inside one shard is that shard's own round; a segment
                         straddling a boundary is resolved from its two boundary shards, decided on
                         the host and cut by routed selects and rank-range aggregates
@@ -125,14 +127,80 @@ class ShardedStore(GpuFingerprintStore):
         for s in self.shards:
             s.set_compaction(divisor, min_rows)
 
+    # ---- device columns (rh_sstore_load_device / rh_sstore_apply_device) ------------------
+    @staticmethod
+    def _device_of(cols) -> int:
+        """The device the (torch) columns live on: all of them on one."""
+        devs = {t.device for t in cols.values() if t is not None}
+        if len(devs) != 1 or next(iter(devs)).type != "cuda":
+            raise ValueError("device columns must live on one GPU")
+        d = next(iter(devs))
+        import torch
+        return torch.cuda.current_device() if d.index is None else d.index
+
+    @staticmethod
+    def _stream_on(device: int) -> int:
+        import torch
+        return torch.cuda.current_stream(device).cuda_stream
+
     def load_bulk_device(self, cols) -> None:
-        raise NotImplementedError("the sharded store takes host columns (load_bulk)")
+        """load_bulk from device (torch) columns: keys sorted and strictly increasing.  The rows are
+        cut at equal counts rounded down to multiples of 16; shards on the columns' device read them
+        in place, shards elsewhere get a device-to-device copy."""
+        from .device import _check_cols, _columns
+        n = _check_cols(self.schema, cols)
+        dev = self._device_of(cols)
+        c = _columns(cols)
+        A.check(A.lib().rh_sstore_load_device(self._h, dev, C.byref(c), n, self._stream_on(dev)),
+                "rh_sstore_load_device")
 
     def apply_device(self, cols, ops=None):
-        raise NotImplementedError("the sharded store takes host columns (apply / stage)")
+        """apply() with device (torch) columns / ops: the rows are routed to their shards on the GPU
+        (rsos_hip.device.route_columns' kernel), then each shard applies its segment.  Returns (new,
+        overwritten, deleted).  A repeated key is refused by its shard after others may have
+        committed: the map then refuses every call until a load."""
+        from .device import _check_cols, _columns
+        m = _check_cols(self.schema, cols)
+        if ops is not None and (ops.numel() != m or not ops.is_cuda):
+            raise ValueError("ops must be m device bytes")
+        dev = self._device_of(cols)
+        c = _columns(cols)
+        a, b, d = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        A.check(A.lib().rh_sstore_apply_device(self._h, dev, C.byref(c), None if ops is None else ops.data_ptr(), m,
+                                               C.byref(a), C.byref(b), C.byref(d), self._stream_on(dev)),
+                "rh_sstore_apply_device")
+        return int(a.value), int(b.value), int(d.value)
 
     def apply_device_many(self, batches, ops=None):
-        raise NotImplementedError("the sharded store takes host columns (apply / stage)")
+        """apply_device over several device batches in order; (new, overwritten, deleted) per batch."""
+        if ops is not None and len(ops) != len(batches):
+            raise ValueError("ops must have one entry per batch")
+        return [self.apply_device(b, None if ops is None else ops[i]) for i, b in enumerate(batches)]
+
+    @staticmethod
+    def load_snapshot(data, dated: Optional["ShardedStore"], projection: Optional["ShardedStore"], key_form: str = "array",
+                      ragged: bool = False, device: int = 0):
+        """Reload a sharded replica's dated map and / or projection from an RCNL v1 snapshot
+        (rh_sstore_load_snapshot): `data` is host bytes, or a uint8 tensor on `device`.  The entries
+        must be in strictly increasing key order (what FileSnapshot::save writes).  Returns
+        rsos_hip.snapshot.SnapshotInfo."""
+        from .snapshot import SnapshotInfo
+        form = {"array": A.FORM_ARRAY, "vec": A.FORM_VEC}[key_form] | (A.FORM_RAGGED if ragged else 0)
+        info = A.SnapshotInfo()
+        hd = None if dated is None else dated._h
+        hp = None if projection is None else projection._h
+        if isinstance(data, (bytes, bytearray, memoryview)):
+            buf = np.frombuffer(bytes(data), np.uint8)
+            rc = A.lib().rh_sstore_load_snapshot(hd, hp, form, _np_ptr(buf), buf.size, 0, device, C.byref(info))
+        else:
+            import torch
+            if not (data.is_cuda and data.dtype == torch.uint8 and data.is_contiguous()):
+                raise ValueError("device snapshot bytes must be a contiguous uint8 device tensor")
+            device = torch.cuda.current_device() if data.device.index is None else data.device.index
+            torch.cuda.current_stream(device).synchronize()  # the call takes complete bytes
+            rc = A.lib().rh_sstore_load_snapshot(hd, hp, form, data.data_ptr(), data.numel(), 1, device, C.byref(info))
+        A.check(rc, "rh_sstore_load_snapshot")
+        return SnapshotInfo(int(info.entries), int(info.tombstones), int(info.entries_end), int(info.keys))
 
     def _key_bytes(self, k: Key) -> bytes:
         return GpuFingerprintStore._key_bytes(self, k)

@@ -233,6 +233,18 @@ extern "C" {
     pub fn rh_sstore_stage(store: *mut rh_sstore, cols: *const rh_columns, ops: *const u8, m: usize) -> c_int;
     pub fn rh_sstore_apply(store: *mut rh_sstore, cols: *const rh_columns, ops: *const u8, n: usize,
                            n_new: *mut u64, n_over: *mut u64, n_del: *mut u64) -> c_int;
+    pub fn rh_sstore_load_device(store: *mut rh_sstore, device: c_int, dev_cols: *const rh_columns, n: usize,
+                                 after_stream: *mut c_void) -> c_int;
+    pub fn rh_sstore_apply_device(store: *mut rh_sstore, device: c_int, dev_cols: *const rh_columns,
+                                  dev_ops: *const u8, n: usize, n_new: *mut u64, n_over: *mut u64, n_del: *mut u64,
+                                  after_stream: *mut c_void) -> c_int;
+    pub fn rh_sstore_load_snapshot(dated: *mut rh_sstore, projection: *mut rh_sstore, key_form: c_int,
+                                   bytes: *const c_void, len: usize, bytes_on_device: c_int, device: c_int,
+                                   info: *mut rh_snapshot_info) -> c_int;
+    pub fn rh_route_columns_device(schema: *const rh_schema, host_splitters: *const c_void, shards: c_int,
+                                   dev_in: *const rh_columns, dev_ops_in: *const u8, n: usize,
+                                   dev_out: *const rh_columns, dev_ops_out: *mut u8, cap_rows: usize,
+                                   counts: *mut u64, starts: *mut u64, stream: *mut c_void) -> c_int;
     pub fn rh_sstore_len(store: *mut rh_sstore, out: *mut u64) -> c_int;
     pub fn rh_sstore_aggregates(store: *mut rh_sstore, lo: *const u64, hi: *const u64, r: usize,
                                 out: *mut rh_aggregate) -> c_int;

@@ -120,6 +120,61 @@ impl<K: GpuKey, V: GpuRecord> HipShardedMap<K, V> {
         self.entries = sorted::SortedBlocks::from_sorted(items);
     }
 
+    /// `load_bulk` from columns already in HBM on `device` (`rh_sstore_load_device`): `items` are the
+    /// same records, sorted by key without duplicates, for the host index.  Cuts fall on multiples of
+    /// 16 rows; shards on `device` read the columns in place, the others get a device-to-device copy.
+    ///
+    /// # Safety
+    /// `cols` must hold `items.len()` rows of device memory on `device`, written on `after_stream`
+    /// (a `hipStream_t` of that device, or null), in the order of `items`.
+    pub unsafe fn load_bulk_device(&mut self, device: i32, cols: &ffi::rh_columns, items: Vec<(K, V)>,
+                                   after_stream: *mut c_void) {
+        check(ffi::rh_sstore_load_device(self.store.0, device as c_int, cols, items.len(), after_stream),
+              "rh_sstore_load_device");
+        self.entries = sorted::SortedBlocks::from_sorted(items);
+    }
+
+    /// A batch already in HBM on `device` (`rh_sstore_apply_device`): routed to the shards on the
+    /// GPU, then applied by each.  `changes` are the same rows for the host index (`None` = delete).
+    /// Returns (new, overwritten, deleted).  Keys must be distinct: a repeated key is refused by its
+    /// shard after others may have committed, and the map then refuses every call until a load.
+    ///
+    /// # Safety
+    /// `cols` (and `ops`, nullable = all inserts) must hold `n` rows of device memory on `device`,
+    /// written on `after_stream`, describing exactly `changes`.
+    pub unsafe fn apply_device(&mut self, device: i32, cols: &ffi::rh_columns, ops: *const u8, n: usize,
+                               changes: Vec<(K, Option<V>)>, after_stream: *mut c_void) -> (u64, u64, u64) {
+        let (mut a, mut b, mut d) = (0u64, 0u64, 0u64);
+        check(ffi::rh_sstore_apply_device(self.store.0, device as c_int, cols, ops, n, &mut a, &mut b, &mut d,
+                                          after_stream),
+              "rh_sstore_apply_device");
+        for (k, v) in changes {
+            match v {
+                Some(v) => drop(self.entries.insert(k, v)),
+                None => drop(self.entries.remove(&k)),
+            }
+        }
+        (a, b, d)
+    }
+
+    /// Reload a dated map and its projection from an RCNL v1 snapshot whose entries are in key order
+    /// (`rh_sstore_load_snapshot`; what `FileSnapshot::save` writes): decoded on `device`, then loaded
+    /// into both maps from the same columns.  `items`: the entries for the host indices, in file order.
+    pub fn load_snapshot<P: GpuRecord>(dated: &mut Self, projection: &mut HipShardedMap<K, P>, key_form: i32,
+                                       bytes: &[u8], device: i32, items: Vec<(K, V)>, proj_items: Vec<(K, P)>)
+                                       -> ffi::rh_snapshot_info {
+        let mut info = ffi::rh_snapshot_info::default();
+        // SAFETY: host bytes of the given length; both handles are live for the &mut borrows.
+        check(unsafe {
+                  ffi::rh_sstore_load_snapshot(dated.store.0, projection.store.0, key_form as c_int,
+                                               bytes.as_ptr() as *const c_void, bytes.len(), 0, device as c_int, &mut info)
+              },
+              "rh_sstore_load_snapshot");
+        dated.entries = sorted::SortedBlocks::from_sorted(items);
+        projection.entries = sorted::SortedBlocks::from_sorted(proj_items);
+        info
+    }
+
     fn stage(&mut self, key: &K, value: Option<&V>) {
         let batch = Batch::new(std::iter::once((key, value)));
         let cols = batch.columns();
