@@ -171,8 +171,12 @@ typedef struct rh_columns {
  * take the large-batch route with separate lift and search launches: the fused lift + search
  * kernel and the small-batch kernel are not built for it.  rh_store_load_snapshot and
  * rh_snapshot_decode_device take it with RH_FORM_RAGGED in key_form ("snapshot reload" below).
- * Not supported (RH_ERR_UNSUPPORTED, the message names VARBYTES): rh_sstore_create (refused before
- * any device call), rh_lift_host, and the two snapshot calls without that flag.                */
+ * Several shards: a map created by rh_sstore_create_flags with RH_SSTORE_VARBYTES takes it in every
+ * rh_sstore_* write call ("sharded store" below), and rh_route_columns_var_device partitions a device
+ * heap by the splitters.
+ * Not supported (RH_ERR_UNSUPPORTED, the message names VARBYTES): rh_sstore_create and
+ * rh_sstore_create_flags without that flag (refused before any device call),
+ * rh_route_columns_device, rh_lift_host, and the two snapshot calls without RH_FORM_RAGGED.     */
 typedef struct rh_var_values {
     const uint8_t  *bytes;     /* the value heap                                              */
     const uint64_t *offsets;   /* n + 1 entries, non-decreasing                               */
@@ -661,9 +665,32 @@ int rh_estore_set_host_tier(rh_estore *store, int enable);
  * whose rows all fall in one shard leaves the map whole.
  * Round outputs belong to the sharded store (valid until its next call), as rh_store_protocol_round's.
  * reserve: each shard reserves rows / n (+ 1/8) resident rows and batches of batch_rows; a device
- * batch's routed copy gets room for batch_rows rows too.                                         */
+ * batch's routed copy gets room for batch_rows rows too.
+ * RH_VAL_VARBYTES values (String -> String): rh_sstore_create refuses them; rh_sstore_create_flags with
+ * RH_SSTORE_VARBYTES takes them, under every key kind the route supports (u32, u64, byte rows and STR
+ * rows of 16 / 32 / 64).  flags = 0 is exactly rh_sstore_create (VARBYTES refused with the same
+ * message); an unknown flag bit is RH_ERR_ARG; the flag changes nothing for a fixed-width schema; every
+ * argument check comes before any device call.  In such a map values is one rh_var_values everywhere:
+ *   load (host)         shard s reads {bytes, offsets + cut(s), bytes_len}: nothing is copied.
+ *   apply / stage       each shard's values are packed into a heap and offsets of its own.  The
+ *                       batch's host offsets are validated once, before any shard changes: offsets[0]
+ *                       <= ... <= offsets[m] <= bytes_len, else RH_ERR_ARG with the map unchanged and
+ *                       not broken.  (A one-row stage passes the caller's columns through to its shard,
+ *                       which validates them the same way.  A staged batch of deletes alone may leave
+ *                       values NULL.)
+ *   load_device         cuts at multiples of 16 rows as ever; a shard on the columns' device reads
+ *                       {bytes, offsets + cut(s), bytes_len} in place.
+ *   apply_device        routed by rh_route_columns_var_device into a heap (capacity: the batch's
+ *                       bytes_len, grown on demand) and an offsets column the sharded store keeps
+ *                       between calls; each shard applies its segment in place.
+ *   another device      a shard elsewhere gets its offsets slice and the heap span between the
+ *                       segment's first and last offset (start rounded down to 4, end up), and rebases
+ *                       the offsets on its own device.
+ *   load_snapshot       with RH_FORM_RAGGED (below).                                              */
+#define RH_SSTORE_VARBYTES 1u
 typedef struct rh_sstore rh_sstore;
 int rh_sstore_create(const int *devices, int n, const rh_schema *schema, rh_sstore **out);
+int rh_sstore_create_flags(const int *devices, int n, const rh_schema *schema, uint32_t flags, rh_sstore **out);
 int rh_sstore_destroy(rh_sstore *store);
 int rh_sstore_shard_count(rh_sstore *store);
 /* shard i's store (borrowed: stats, tier stats; destroyed with the sharded store)            */
@@ -699,7 +726,9 @@ int rh_sstore_apply_device(rh_sstore *store, int device, const rh_columns *dev_c
 /* Snapshot reload into a sharded replica (rh_store_load_snapshot's counterpart; Persistence::load,
  * lww-register/src/persistence.rs:132-137): the entries are decoded on `device`
  * (rh_snapshot_decode_device: the flag-clear route, and RH_FORM_RAGGED for RH_KEY_STR keys with unit /
- * u32 / u64 values) and loaded into each map from the same columns (rh_sstore_load_device; one lift per
+ * u32 / u64 values, and for RH_VAL_VARBYTES values under any routable key in maps created with
+ * RH_SSTORE_VARBYTES: the heap is decoded into a buffer of roundup4(len) bytes) and loaded into each
+ * map from the same columns (rh_sstore_load_device; one lift per
  * map).  Either map may be NULL; both must have the same shard count, the same devices and matching
  * key and value kinds.  bytes_on_device: 0 = host bytes, 1 = bytes on `device`, complete before the call.
  * The entries must be in strictly increasing key order -- what FileSnapshot::save (src/snapshot.rs:164-189)
@@ -719,7 +748,7 @@ int rh_sstore_load_snapshot(rh_sstore *dated, rh_sstore *projection, int key_for
  * counted nowhere.  Columns: keys, values (value_len > 0), phys / logical / node (DATED) are required
  * in both; tags (DATED / PROJECTION) and ops are moved when given (then required in the output); an
  * absent column stays absent.  Fixed-width values only (RH_VAL_VARBYTES: RH_ERR_UNSUPPORTED, the message
- * names VARBYTES).  cap_rows: the rows each output column has room for; n + 16 * shards always suffices,
+ * names VARBYTES; rh_route_columns_var_device below routes them).  cap_rows: the rows each output column has room for; n + 16 * shards always suffices,
  * less is RH_ERR_ARG with nothing written.  Nothing is read at or past row n, nothing written at or
  * past row cap_rows.  counts / starts: host arrays of `shards` entries.  Every argument check comes
  * before any device call; n = 0 makes none.  Runs on `stream`, synchronous on it (one read-back: the
@@ -727,6 +756,29 @@ int rh_sstore_load_snapshot(rh_sstore *dated, rh_sstore *projection, int key_for
 int rh_route_columns_device(const rh_schema *schema, const void *host_splitters, int shards, const rh_columns *dev_in,
                             const uint8_t *dev_ops_in, size_t n, const rh_columns *dev_out, uint8_t *dev_ops_out,
                             size_t cap_rows, uint64_t *counts, uint64_t *starts, void *stream);
+/* The ragged form of rh_route_columns_device: the same row partition (the same counts / starts, 16-row
+ * segment starts and zeroed gap rows), with a RH_VAL_VARBYTES value column moved too.  A fixed-width
+ * schema is handed to rh_route_columns_device unchanged, with *heap_bytes = 0.  For VARBYTES:
+ * dev_in->values is a HOST rh_var_values holding device pointers under the _device contract (rh_var_values
+ * above); dev_out->values is a HOST rh_var_values whose bytes and offsets are WRITABLE device buffers --
+ * bytes 4-byte aligned with bytes_len (its capacity) a multiple of 4, offsets 8-byte aligned with room
+ * for cap_rows + 1 entries (RH_ERR_ARG otherwise, before any device call).  With R = starts[shards - 1] +
+ * roundup16(counts[shards - 1]) the call writes offsets[0 .. R]: offsets[0] = 0, non-decreasing, output
+ * row r's value = bytes[offsets[r] .. offsets[r + 1]), gap rows empty; the values are packed in
+ * output-row order with no gaps, and the bytes from offsets[R] to the next multiple of 4 are zeroed.
+ * *heap_bytes = offsets[R].  Shard s's segment is then a valid device value column as {bytes, offsets +
+ * starts[s], bytes_len} with no rebasing.  A row's span is moved whatever its tag or op, clipped as
+ * rh_snapshot_encode_device clips it: a span that decreases or starts past the input's bytes_len is
+ * empty, one that ends past it is cut there (the length pass and the copy pass clip through the same
+ * code, so nothing is read outside the input heap).  If the routed bytes, rounded up to 4, exceed the
+ * output capacity the call returns RH_ERR_ARG: nothing is promised about the output's contents, but no
+ * byte at or past bytes + bytes_len and no offsets entry past index R is written.  A capacity equal to
+ * the input's bytes_len always suffices for well-formed offsets.  Argument checks, n = 0, n >= 2^32 and
+ * synchrony as for rh_route_columns_device; the one read-back carries the counts and the total.      */
+int rh_route_columns_var_device(const rh_schema *schema, const void *host_splitters, int shards,
+                                const rh_columns *dev_in, const uint8_t *dev_ops_in, size_t n,
+                                const rh_columns *dev_out, uint8_t *dev_ops_out, size_t cap_rows, uint64_t *counts,
+                                uint64_t *starts, uint64_t *heap_bytes, void *stream);
 int rh_sstore_len(rh_sstore *store, uint64_t *out);
 int rh_sstore_aggregates(rh_sstore *store, const uint64_t *lo, const uint64_t *hi, size_t r, rh_aggregate *out);
 int rh_sstore_aggregate_keys(rh_sstore *store, int lo_kind, const void *lo_key, int hi_kind, const void *hi_key,

@@ -19,11 +19,15 @@
 //            neighbours.  The last `shards` workgroups zero the gap rows instead.
 // Nothing is read at or past row n; nothing is written at or past row start[G - 1] +
 // roundup16(count[G - 1]) <= n + 15 * shards.
+// A VARBYTES value column (rh_route_columns_var_device) adds three steps, described at route_span:
+// the scatter pass leaves each output row's clipped value length and source offset in scratch, a
+// scan of the lengths gives the heap offsets, and a copy pass packs the bytes in output-row order.
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/rsos_hip.h"
+#include "byte_window.hpp"
 #include "shard_route.hpp"
 
 namespace rh {
@@ -213,10 +217,10 @@ __device__ __forceinline__ void zero_rows(const RouteCol &c, uint64_t row0, uint
     for (uint64_t e = threadIdx.x; e < total; e += WG) dst[e] = T{};
 }
 
-// workgroups [0, nwg): a tile each; workgroups [nwg, nwg + shards): a shard's gap rows each
+// workgroups [0, nwg): a tile each; workgroups [nwg, nwg + shards): a shard's gap rows each.
+// Returns the tile's rows with L.dest complete (0 for a gap workgroup).
 template <int KB, bool NUM>
-__global__ __launch_bounds__(256) void k_route_scatter(RouteArgs a) {
-    __shared__ RouteLds<digits_of<KB>(), true> L;
+__device__ __forceinline__ uint32_t scatter_tile(const RouteArgs &a, RouteLds<digits_of<KB>(), true> &L) {
     if (blockIdx.x >= a.nwg) {
         const int s = (int)(blockIdx.x - a.nwg);
         const uint64_t end = a.meta[a.shards + s] + a.meta[s];
@@ -228,7 +232,7 @@ __global__ __launch_bounds__(256) void k_route_scatter(RouteArgs a) {
             else if (c.unit == 4) zero_rows<uint32_t>(c, end, stop);
             else zero_rows<uint8_t>(c, end, stop);
         }
-        return;
+        return 0;
     }
     const uint64_t tile0 = (uint64_t)blockIdx.x * ROUTE_TILE;
     const uint32_t rows = (uint32_t)(a.n - tile0 < ROUTE_TILE ? a.n - tile0 : ROUTE_TILE);
@@ -241,6 +245,131 @@ __global__ __launch_bounds__(256) void k_route_scatter(RouteArgs a) {
         else if (c.unit == 4) move_column<uint32_t>(c, tile0, rows, L.dest);
         else move_column<uint8_t>(c, tile0, rows, L.dest);
     }
+    return rows;
+}
+
+template <int KB, bool NUM>
+__global__ __launch_bounds__(256) void k_route_scatter(RouteArgs a) {
+    __shared__ RouteLds<digits_of<KB>(), true> L;
+    scatter_tile<KB, NUM>(a, L);
+}
+
+// ---- a VARBYTES value column (rh_route_columns_var_device) ------------------------------------------
+// The scatter pass also leaves, per output row, the row's clipped value length and where its bytes
+// start in the input heap (vlen / vsrc: scratch of rows + 1 entries, vlen zeroed before the pass, so
+// gap rows and the entry behind the last row hold 0); an exclusive scan of vlen gives every output
+// row's heap offset (vpos); the copy pass then moves the bytes.  The one place a span is clipped:
+// a span that decreases or starts past the heap is empty, one that ends past it is cut at its end
+// (snap_encode.hip's enc_value)
+__device__ __forceinline__ void route_span(const uint64_t *offs, uint64_t limit, uint64_t i, uint64_t *src, uint64_t *len) {
+    const uint64_t o0 = offs[i], o1 = offs[i + 1];
+    if (o0 > limit || o1 < o0) {
+        *src = 0, *len = 0;
+    } else {
+        *src = o0;
+        *len = (o1 < limit ? o1 : limit) - o0;
+    }
+}
+
+template <int KB, bool NUM>
+__global__ __launch_bounds__(256) void k_route_scatter_var(RouteArgs a, RouteVar v, uint64_t *vlen, uint64_t *vsrc) {
+    __shared__ RouteLds<digits_of<KB>(), true> L;
+    const uint32_t rows = scatter_tile<KB, NUM>(a, L);
+    const uint64_t tile0 = (uint64_t)blockIdx.x * ROUTE_TILE;
+    for (uint32_t r = threadIdx.x; r < rows; r += WG) {
+        uint64_t src, len;
+        route_span(v.offs_in, v.limit_in, tile0 + r, &src, &len);
+        vlen[L.dest[r]] = len;
+        vsrc[L.dest[r]] = src;
+    }
+}
+
+// The copy pass: a workgroup per VAR_BLOCK consecutive output rows.  Their values are one contiguous
+// span of the output heap, [vpos[b0], vpos[b1]), at byte granularity against sources of any alignment
+// -- snap_encode.hip's write pass without an entry's fixed part.  The span is cut into windows of
+// VAR_WIN bytes on 16-byte boundaries of the output's address; a window is assembled in LDS at its
+// final relative positions (every wave its 64 rows' parts, eight at a time, VAR_GROUP lanes a part, a
+// lane's loads all issued before its first LDS store) and streamed out as one aligned 16-byte store
+// per lane.  A part of VAR_DIRECT bytes or more does not pass the LDS: the whole wave copies its
+// whole granules straight from the source, 4 KiB a step.  Two workgroups meet only in the granule
+// holding a span's edge, where each writes its own bytes with byte stores: nothing is read back and
+// no word is rewritten.  Positions are kept relative to the 16-byte boundary at or below bytes_out
+// (`mis` bytes before it: the heap is only 4-byte aligned).
+constexpr uint32_t VAR_BLOCK = 256;
+// the window and the copies of a part are byte_window.hpp's (shared with snap_encode.hip)
+constexpr uint32_t VAR_WIN = BW_WIN, VAR_DIRECT = BW_DIRECT, VAR_GROUP = BW_GROUP, VAR_LDS = BW_LDS;
+
+// meta: counts, starts (G each), then [2 G] <- the routed heap's bytes.  vpos: the scan of vlen.
+__global__ __launch_bounds__(256) void k_route_var_copy(RouteVar v, const uint64_t *meta, int G, const uint64_t *vlen,
+                                                        const uint64_t *vsrc, const uint64_t *vpos, uint64_t *meta_total) {
+    extern __shared__ __align__(16) uint8_t win[];  // (no static LDS in this kernel: the base stays 16-byte aligned)
+    uint32_t *direct = reinterpret_cast<uint32_t *>(win + VAR_WIN);
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
+    const uint64_t R = meta[2 * G - 1] + ((meta[G - 1] + ROUTE_ALIGN - 1) & ~(ROUTE_ALIGN - 1));
+    const uint64_t b0 = (uint64_t)blockIdx.x * VAR_BLOCK;
+    if (b0 >= R) return;  // (the grid covers the most rows R can be)
+    const uint64_t b1 = b0 + VAR_BLOCK < R ? b0 + VAR_BLOCK : R;
+    const uint64_t total = vpos[R];
+    const uint64_t i = b0 + tid;
+    const bool have = i < b1;
+    uint64_t vdst = 0, cl = 0, src = 0;
+    if (have) {
+        vdst = vpos[i];
+        v.offs_out[i] = vdst;
+        cl = vlen[i];
+        if (cl) src = vsrc[i];
+    }
+    if (b1 == R && tid == 0) {
+        v.offs_out[R] = total;
+        *meta_total = total;
+    }
+    if (((total + 3) & ~3ull) > v.cap_out) return;  // does not fit: no heap byte is written (every workgroup agrees)
+    const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(v.bytes_out) & 15u);
+    uint8_t *base = v.bytes_out - mis;  // 16-byte aligned; nothing below base + mis is touched
+    const uint64_t lo = vpos[b0] + mis, hi = vpos[b1] + mis;  // the span this workgroup owns
+    vdst += mis;
+    for (uint64_t w = lo & ~15ull; w < hi; w += VAR_WIN) {
+        const uint64_t whi = w + VAR_WIN;
+        if (tid < VAR_WIN / 16 / 32) direct[tid] = 0;
+        __syncthreads();
+        // the part of every value that lies in this window, a wave's 64 rows in turn
+        uint64_t cs = 0;
+        uint32_t cr = 0, cn = 0;
+        if (cl) {
+            const uint64_t a = vdst > w ? vdst : w, e = vdst + cl < whi ? vdst + cl : whi;
+            if (a < e) cs = src + (a - vdst), cr = (uint32_t)(a - w), cn = (uint32_t)(e - a);
+        }
+        unsigned long long ml = __ballot(cn >= VAR_DIRECT);  // the long parts, one at a time
+        while (ml) {
+            const int k = __ffsll((long long)ml) - 1;
+            ml &= ml - 1;
+            bw_direct(v.bytes_in + bw_shfl64(cs, k), win, direct, base + w, __shfl(cr, k), __shfl(cn, k), lane);
+        }
+        const unsigned long long m = __ballot(cn != 0 && cn < VAR_DIRECT);  // the others, NG at a time
+        constexpr uint32_t NG = 64 / VAR_GROUP;
+        for (uint32_t r = 0; r < 64 / NG; r++) {
+            if (!((m >> (r * NG)) & ((1ull << NG) - 1))) continue;  // (the same in every lane)
+            const int k = (int)(r * NG + lane / VAR_GROUP);
+            const uint64_t S = bw_shfl64(cs, k);
+            const uint32_t Rw = __shfl(cr, k), N = __shfl(cn, k);
+            if (N && N < VAR_DIRECT) bw_copy(v.bytes_in + S, win, Rw, N, lane % VAR_GROUP);
+        }
+        __syncthreads();
+        for (uint32_t g = tid; g < VAR_WIN / 16; g += VAR_BLOCK) {
+            const uint64_t a = w + (uint64_t)g * 16;
+            if (a >= hi) break;
+            if ((direct[g >> 5] >> (g & 31)) & 1) continue;
+            if (a >= lo && a + 16 <= hi) {
+                reinterpret_cast<uint4 *>(base)[a / 16] = reinterpret_cast<const uint4 *>(win)[g];
+            } else {  // a span's edge: its own bytes only (the rest of the granule is a neighbour's)
+                for (uint32_t b = 0; b < 16; b++)
+                    if (a + b >= lo && a + b < hi) base[a + b] = win[g * 16 + b];
+            }
+        }
+        __syncthreads();
+    }
+    // the bytes from the heap's end to the next multiple of 4 (inside cap_out: checked above)
+    if (b1 == R && tid < ((4u - (uint32_t)(total & 3u)) & 3u)) v.bytes_out[total + tid] = 0;
 }
 
 template <int KB, bool NUM>
@@ -268,7 +397,7 @@ hipError_t first_unsorted_launch(const uint8_t *keys, uint64_t n, unsigned long 
 }
 
 template <int KB, bool NUM>
-hipError_t route_launch(const RouteArgs &a0, Scratch &s, hipStream_t st) {
+hipError_t route_launch(const RouteArgs &a0, Scratch &s, hipStream_t st, const RouteVar *var) {
     RouteArgs a = a0;
     const uint64_t cells = (uint64_t)a.shards * a.nwg;
     hipLaunchKernelGGL((k_route_count<KB, NUM>), dim3(a.nwg), dim3(WG), 0, st, a);
@@ -276,7 +405,24 @@ hipError_t route_launch(const RouteArgs &a0, Scratch &s, hipStream_t st) {
     if (e) return e;
     if ((e = launch_exclusive_scan_u64(a.cnt, const_cast<uint64_t *>(a.scan), cells, s, st))) return e;
     hipLaunchKernelGGL(k_route_starts, dim3(1), dim3(64), 0, st, a.scan, a.nwg, a.n, a.shards, a.meta);
-    hipLaunchKernelGGL((k_route_scatter<KB, NUM>), dim3(a.nwg + (uint32_t)a.shards), dim3(WG), 0, st, a);
+    if (!var) {
+        hipLaunchKernelGGL((k_route_scatter<KB, NUM>), dim3(a.nwg + (uint32_t)a.shards), dim3(WG), 0, st, a);
+        return hipGetLastError();
+    }
+    // the most rows the output can hold (every segment but the first starts after at most 15 gap
+    // rows, and so ends the last): the host learns the exact number only from the read-back
+    const uint64_t rmax = a.n + ROUTE_ALIGN * (uint64_t)a.shards;
+    uint64_t *vlen = static_cast<uint64_t *>(s.get(124, (rmax + 1) * 8));
+    uint64_t *vsrc = static_cast<uint64_t *>(s.get(125, (rmax + 1) * 8));
+    uint64_t *vpos = static_cast<uint64_t *>(s.get(126, (rmax + 1) * 8));
+    if (s.err) return s.err;
+    if ((e = hipMemsetAsync(vlen, 0, (rmax + 1) * 8, st))) return e;
+    hipLaunchKernelGGL((k_route_scatter_var<KB, NUM>), dim3(a.nwg + (uint32_t)a.shards), dim3(WG), 0, st, a, *var, vlen,
+                       vsrc);
+    if ((e = hipGetLastError())) return e;
+    if ((e = launch_exclusive_scan_u64(vlen, vpos, rmax + 1, s, st))) return e;
+    hipLaunchKernelGGL(k_route_var_copy, dim3((uint32_t)((rmax + VAR_BLOCK - 1) / VAR_BLOCK)), dim3(VAR_BLOCK), VAR_LDS, st,
+                       *var, a.meta, a.shards, vlen, vsrc, vpos, a.meta + 2 * a.shards);
     return hipGetLastError();
 }
 
@@ -298,7 +444,8 @@ bool route_key_supported(uint32_t kb, bool numeric) {
     return numeric ? (kb == 4 || kb == 8) : (kb == 8 || kb == 16 || kb == 32 || kb == 64);
 }
 
-hipError_t launch_route(const RouteJob &job, const uint8_t *split, uint64_t *meta, Scratch &s, hipStream_t st) {
+hipError_t launch_route(const RouteJob &job, const uint8_t *split, uint64_t *meta, Scratch &s, hipStream_t st,
+                        const RouteVar *var) {
     RouteArgs a;
     a.keys = job.keys;
     a.split = split;
@@ -312,12 +459,12 @@ hipError_t launch_route(const RouteJob &job, const uint8_t *split, uint64_t *met
     a.meta = meta;
     a.ncols = job.ncols;
     for (int j = 0; j < job.ncols; j++) a.cols[j] = job.cols[j];
-    if (job.numeric) return job.key_bytes == 4 ? route_launch<4, true>(a, s, st) : route_launch<8, true>(a, s, st);
+    if (job.numeric) return job.key_bytes == 4 ? route_launch<4, true>(a, s, st, var) : route_launch<8, true>(a, s, st, var);
     switch (job.key_bytes) {
-    case 8: return route_launch<8, false>(a, s, st);
-    case 16: return route_launch<16, false>(a, s, st);
-    case 32: return route_launch<32, false>(a, s, st);
-    default: return route_launch<64, false>(a, s, st);
+    case 8: return route_launch<8, false>(a, s, st, var);
+    case 16: return route_launch<16, false>(a, s, st, var);
+    case 32: return route_launch<32, false>(a, s, st, var);
+    default: return route_launch<64, false>(a, s, st, var);
     }
 }
 
@@ -359,7 +506,8 @@ uint32_t value_row(const rh_schema &s) {
 }
 
 // the route's device scratch, one per device, kept between calls and held for a whole call (the
-// call is synchronous): slots 120-121 the counts and their scan, 122 the splitters, 123 meta
+// call is synchronous): slots 120-121 the counts and their scan, 122 the splitters, 123 meta,
+// 124-126 a VARBYTES column's per-row lengths, source offsets and heap offsets
 struct RouteScratch {
     std::mutex mu;
     std::vector<rh::Scratch> by_dev;
@@ -383,19 +531,19 @@ int key_cmp(const rh_schema &s, const uint8_t *a, const uint8_t *b) {
     return memcmp(a, b, s.key_len);
 }
 
-}  // namespace
-
-extern "C" int rh_route_columns_device(const rh_schema *schema, const void *host_splitters, int shards,
-                                       const rh_columns *in, const uint8_t *ops_in, size_t n, const rh_columns *out,
-                                       uint8_t *ops_out, size_t cap_rows, uint64_t *counts, uint64_t *starts,
-                                       void *stream) {
+// rh_route_columns_device (heap_bytes NULL: VARBYTES refused) and rh_route_columns_var_device
+int route_columns(const rh_schema *schema, const void *host_splitters, int shards, const rh_columns *in,
+                  const uint8_t *ops_in, size_t n, const rh_columns *out, uint8_t *ops_out, size_t cap_rows,
+                  uint64_t *counts, uint64_t *starts, uint64_t *heap_bytes, void *stream) {
     // every check on the arguments first: nothing below them fails for a reason the caller could have seen
     int rc = rh::check_schema_arg(schema);
     if (rc) return rc;
     const rh_schema &s = *schema;
-    if (s.value_kind == RH_VAL_VARBYTES)
+    const bool var = s.value_kind == RH_VAL_VARBYTES;
+    if (var && !heap_bytes)
         return fail(RH_ERR_UNSUPPORTED, "route: VARBYTES values are not routed (fixed-width value rows only; the "
                                         "sharded store does not take them either)");
+    if (heap_bytes) *heap_bytes = 0;
     if (shards < 1 || shards > rh::ROUTE_MAX_SHARDS) return fail(RH_ERR_ARG, "route: shards must be 1..64");
     if (!counts || !starts) return fail(RH_ERR_ARG, "route: counts / starts is NULL");
     if (shards > 1 && !host_splitters) return fail(RH_ERR_ARG, "route: splitters is NULL");
@@ -434,6 +582,21 @@ extern "C" int rh_route_columns_device(const rh_schema *schema, const void *host
     add(ops_in, ops_out, 1, false, "ops");
     if (bad && !strcmp(bad, "alignment")) return fail(RH_ERR_ARG, "route: device columns must be 16-byte aligned");
     if (bad) return fail(RH_ERR_ARG, std::string("route: column ") + bad + " is NULL in the input or the output");
+    rh::RouteVar rv{};
+    if (var) {
+        const rh_var_values *iv = static_cast<const rh_var_values *>(in->values);
+        const rh_var_values *ov = static_cast<const rh_var_values *>(out->values);
+        if (!iv || !ov) return fail(RH_ERR_ARG, "route: column values is NULL in the input or the output");
+        auto misaligned = [](const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
+        if (!iv->offsets || !ov->offsets || misaligned(iv->offsets, 8) || misaligned(ov->offsets, 8))
+            return fail(RH_ERR_ARG, "route: VARBYTES offsets must be non-NULL and 8-byte aligned");
+        if ((!iv->bytes && iv->bytes_len) || (!ov->bytes && ov->bytes_len))
+            return fail(RH_ERR_ARG, "route: VARBYTES heap is NULL");
+        if (misaligned(iv->bytes, 4) || misaligned(ov->bytes, 4) || iv->bytes_len % 4 || ov->bytes_len % 4)
+            return fail(RH_ERR_ARG, "route: a VARBYTES heap must be 4-byte aligned and bytes_len a multiple of 4");
+        rv = rh::RouteVar{iv->bytes,   iv->offsets, iv->bytes_len, const_cast<uint8_t *>(ov->bytes),
+                          const_cast<uint64_t *>(ov->offsets), ov->bytes_len};
+    }
     job.keys = static_cast<const uint8_t *>(in->keys);
     job.key_bytes = kl;
     job.numeric = numeric;
@@ -450,14 +613,39 @@ extern "C" int rh_route_columns_device(const rh_schema *schema, const void *host
     scr.stream = st;
     scr.err = hipSuccess;
     uint8_t *split = static_cast<uint8_t *>(scr.get(122, (size_t)rh::ROUTE_MAX_SHARDS * 64));
-    uint64_t *meta = static_cast<uint64_t *>(scr.get(123, 2 * rh::ROUTE_MAX_SHARDS * 8));
+    uint64_t *meta = static_cast<uint64_t *>(scr.get(123, (2 * rh::ROUTE_MAX_SHARDS + 1) * 8));
     if (scr.err) return fail(RH_ERR_OOM, "route: scratch allocation failed");
     if (shards > 1) RH_HIP(hipMemcpyAsync(split, sp, (size_t)(shards - 1) * kl, hipMemcpyHostToDevice, st));
-    RH_HIP(rh::launch_route(job, split, meta, scr, st));
+    RH_HIP(rh::launch_route(job, split, meta, scr, st, var ? &rv : nullptr));
     if (scr.err) return fail(RH_ERR_OOM, "route: scratch allocation failed");
-    uint64_t h[2 * rh::ROUTE_MAX_SHARDS];
-    RH_HIP(hipMemcpyAsync(h, meta, 2 * (size_t)shards * 8, hipMemcpyDeviceToHost, st));
+    uint64_t h[2 * rh::ROUTE_MAX_SHARDS + 1];
+    RH_HIP(hipMemcpyAsync(h, meta, (2 * (size_t)shards + (var ? 1 : 0)) * 8, hipMemcpyDeviceToHost, st));
     RH_HIP(hipStreamSynchronize(st));
     for (int t = 0; t < shards; t++) counts[t] = h[t], starts[t] = h[shards + t];
+    if (var) {
+        *heap_bytes = h[2 * shards];
+        if (((h[2 * shards] + 3) & ~3ull) > rv.cap_out)
+            return fail(RH_ERR_ARG, "route: the routed values need " + std::to_string(h[2 * shards]) +
+                                        " bytes (rounded up to 4), more than the output heap's bytes_len");
+    }
     return RH_OK;
+}
+
+}  // namespace
+
+extern "C" int rh_route_columns_device(const rh_schema *schema, const void *host_splitters, int shards,
+                                       const rh_columns *in, const uint8_t *ops_in, size_t n, const rh_columns *out,
+                                       uint8_t *ops_out, size_t cap_rows, uint64_t *counts, uint64_t *starts,
+                                       void *stream) {
+    return route_columns(schema, host_splitters, shards, in, ops_in, n, out, ops_out, cap_rows, counts, starts, nullptr,
+                         stream);
+}
+
+extern "C" int rh_route_columns_var_device(const rh_schema *schema, const void *host_splitters, int shards,
+                                           const rh_columns *in, const uint8_t *ops_in, size_t n, const rh_columns *out,
+                                           uint8_t *ops_out, size_t cap_rows, uint64_t *counts, uint64_t *starts,
+                                           uint64_t *heap_bytes, void *stream) {
+    if (!heap_bytes) return fail(RH_ERR_ARG, "route: heap_bytes is NULL");
+    return route_columns(schema, host_splitters, shards, in, ops_in, n, out, ops_out, cap_rows, counts, starts, heap_bytes,
+                         stream);
 }

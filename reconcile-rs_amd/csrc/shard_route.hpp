@@ -38,10 +38,26 @@ struct RouteJob {
     int ncols;
 };
 
+// A VARBYTES value column routed beside the job's fixed-width columns (rh_route_columns_var_device):
+// value i of the input = bytes_in[offs_in[i] .. offs_in[i + 1]) clipped to limit_in (route_span), into
+// a heap packed in output-row order.  Nothing is written at or past bytes_out + cap_out, nor past
+// offs_out[R], R = the routed rows with their gaps; when the values (rounded up to 4) do not fit in
+// cap_out no heap byte is written at all.
+struct RouteVar {
+    const uint8_t *bytes_in;
+    const uint64_t *offs_in;
+    uint64_t limit_in;
+    uint8_t *bytes_out;
+    uint64_t *offs_out;
+    uint64_t cap_out;
+};
+
 // Partition the job's columns (n >= 1).  split: the shards - 1 splitter rows on the device.  meta
-// (device, 2 * shards u64) receives the per-shard counts, then the segment starts (rows).  Scratch
-// slots 120-121 hold the (shard, workgroup) counts and their scan.  Asynchronous on st.
-hipError_t launch_route(const RouteJob &job, const uint8_t *split, uint64_t *meta, Scratch &s, hipStream_t st);
+// (device, 2 * shards + 1 u64) receives the per-shard counts, then the segment starts (rows), then --
+// with var -- the routed heap's bytes.  Scratch slots 120-121 hold the (shard, workgroup) counts and
+// their scan, 124-126 each output row's value length, source offset and heap offset.  Asynchronous on st.
+hipError_t launch_route(const RouteJob &job, const uint8_t *split, uint64_t *meta, Scratch &s, hipStream_t st,
+                        const RouteVar *var = nullptr);
 
 // *first (device) = the least i in [1, n) with key[i - 1] >= key[i] in that key order, or ~0 when
 // the keys are strictly increasing (the word is preset on st by this call)

@@ -221,6 +221,25 @@ struct ColBuf {
     size_t width[NCOL] = {};
     hipStream_t st = nullptr;
     hipEvent_t ev = nullptr;
+    // a VARBYTES value column: offsets beside the rows (cap + 1 entries), and a heap of its own size
+    uint64_t *voff = nullptr;
+    uint8_t *heap = nullptr;
+    size_t heap_cap = 0;    // bytes, a multiple of 4
+    rh_var_values desc{};   // what a view of these columns hands out as `values` (host memory)
+    int ensure_heap(size_t bytes) {
+        bytes = (bytes + 3) & ~size_t(3);
+        if (bytes <= heap_cap && heap) return RH_OK;
+        if (heap) (void)hipFree(heap);
+        heap = nullptr, heap_cap = 0;
+        SS_HIP(hipMalloc(reinterpret_cast<void **>(&heap), bytes + 64));
+        heap_cap = bytes;
+        return RH_OK;
+    }
+    // the whole value column (heap capacity as bytes_len), from output row `row` on
+    const rh_var_values *var_view(size_t row) {
+        desc = rh_var_values{heap, voff + row, heap_cap};
+        return &desc;
+    }
     int open(int dev) {
         SS_HIP(hipSetDevice(dev));
         if (st) return RH_OK;
@@ -239,6 +258,7 @@ struct ColBuf {
             width[c] = w[c];
             if (w[c]) SS_HIP(hipMalloc(&p[c], rows * w[c] + 64));
         }
+        if (s.value_kind == RH_VAL_VARBYTES) SS_HIP(hipMalloc(reinterpret_cast<void **>(&voff), (rows + 1) * 8 + 64));
         cap = rows;
         return RH_OK;
     }
@@ -268,12 +288,16 @@ struct ColBuf {
             if (p[c]) (void)hipFree(p[c]);
             p[c] = nullptr;
         }
+        if (voff) (void)hipFree(voff);
+        voff = nullptr;
         cap = 0;
     }
     void release() {
         if (device < 0) return;
         (void)hipSetDevice(device);
         drop();
+        if (heap) (void)hipFree(heap);
+        heap = nullptr, heap_cap = 0;
         if (st) (void)hipStreamDestroy(st);
         if (ev) (void)hipEventDestroy(ev);
         st = nullptr, ev = nullptr;
@@ -292,6 +316,19 @@ rh_columns columns_from(const rh_schema &s, const rh_columns &c, size_t a) {
                       at(c.values, (size_t)value_row(s))};
 }
 
+// a VARBYTES value column (`values`: a host rh_var_values) from row `a` on: the same heap, later offsets
+rh_var_values var_from(const void *values, size_t a) {
+    const rh_var_values &v = *static_cast<const rh_var_values *>(values);
+    return rh_var_values{v.bytes, v.offsets + a, v.bytes_len};
+}
+
+// offsets copied from another device, made relative to the heap span copied with them (which began
+// at byte `lo` of the source heap); an offset below lo -- malformed input -- becomes 0
+__global__ __launch_bounds__(256) void k_rebase_offsets(uint64_t *offs, uint64_t n, uint64_t lo) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) offs[i] = offs[i] >= lo ? offs[i] - lo : 0;
+}
+
 const rh_aggregate kZero{{0, 0, 0, 0}, 0};
 void agg_add(rh_aggregate &a, const rh_aggregate &b) {
     rh_fp_add(a.fingerprint, b.fingerprint, a.fingerprint);
@@ -304,6 +341,7 @@ struct rh_sstore {
     rh_schema schema{};
     int G = 0;
     size_t kl = 0;
+    bool var = false;  // RH_VAL_VARBYTES values (rh_sstore_create_flags, RH_SSTORE_VARBYTES): `values` is a rh_var_values
     std::vector<rh_store *> shards;
     std::vector<uint8_t> split;     // G - 1 keys: shard s holds [split[s - 1], split[s])
     std::vector<uint64_t> sizes;    // rows per shard (valid while sizes_ok)
@@ -375,6 +413,25 @@ struct rh_sstore {
             if (from[c] && b.width[c])
                 SS_HIP(hipMemcpyPeerAsync(b.p[c], dev[t], from[c], device, rows * b.width[c], b.st));
         *view = b.cols(0, src);
+        if (var) {
+            // the segment's offsets, and the heap between its first and last offset (widened to
+            // multiples of 4): the offsets are rebased on this shard's device, relative to that span
+            const rh_var_values v = *static_cast<const rh_var_values *>(src.values);
+            uint64_t ends[2] = {0, 0};
+            SS_HIP(hipMemcpyAsync(&ends[0], v.offsets, 8, hipMemcpyDeviceToHost, b.st));
+            SS_HIP(hipMemcpyAsync(&ends[1], v.offsets + rows, 8, hipMemcpyDeviceToHost, b.st));
+            SS_HIP(hipStreamSynchronize(b.st));
+            const uint64_t lo = std::min<uint64_t>(ends[0], v.bytes_len) & ~uint64_t(3);
+            const uint64_t hi = std::min<uint64_t>((std::max(ends[1], lo) + 3) & ~uint64_t(3), v.bytes_len);  // (bytes_len: a multiple of 4)
+            if (int rc = b.ensure_heap(std::max<uint64_t>(hi - lo, 4))) return rc;
+            if (hi > lo) SS_HIP(hipMemcpyPeerAsync(b.heap, dev[t], v.bytes + lo, device, hi - lo, b.st));
+            SS_HIP(hipMemcpyPeerAsync(b.voff, dev[t], v.offsets, device, (rows + 1) * 8, b.st));
+            hipLaunchKernelGGL(k_rebase_offsets, dim3((unsigned)((rows + 256) / 256)), dim3(256), 0, b.st, b.voff,
+                               (uint64_t)rows + 1, lo);
+            SS_HIP(hipGetLastError());
+            b.desc = rh_var_values{b.heap, b.voff, hi - lo};
+            view->values = &b.desc;
+        }
         *ops = src_ops ? static_cast<const uint8_t *>(b.p[ColBuf::OPS]) : nullptr;
         *after = b.st;
         return RH_OK;
@@ -555,13 +612,29 @@ struct rh_sstore {
         std::vector<uint64_t> phys, node;
         std::vector<uint32_t> logical;
         size_t m = 0;
+        // VARBYTES values: vals is the shard's own heap, packed in row order, voffs its m + 1 offsets
+        std::vector<uint64_t> voffs;
+        rh_var_values var{};
+        bool is_var = false;
         rh_columns cols() const {
             auto p = [](const auto &v) { return v.empty() ? nullptr : v.data(); };
             return rh_columns{p(keys), reinterpret_cast<const uint64_t *>(p(phys)),
                               reinterpret_cast<const uint32_t *>(p(logical)),
-                              reinterpret_cast<const uint64_t *>(p(node)), p(tags), p(vals)};
+                              reinterpret_cast<const uint64_t *>(p(node)), p(tags),
+                              is_var ? static_cast<const void *>(&var) : static_cast<const void *>(p(vals))};
         }
     };
+    // a host batch's VARBYTES offsets, checked once before any shard changes (rh_store_apply's rule)
+    static int check_var_offsets(const rh_columns &h, size_t m) {
+        const rh_var_values *v = static_cast<const rh_var_values *>(h.values);
+        if (!v || !v->offsets) return fail(RH_ERR_ARG, "values column is NULL");
+        if (!v->bytes && v->bytes_len) return fail(RH_ERR_ARG, "VARBYTES: the value heap is NULL");
+        for (size_t i = 0; i < m; i++)
+            if (v->offsets[i] > v->offsets[i + 1])
+                return fail(RH_ERR_ARG, "VARBYTES: value offsets must not decrease (row " + std::to_string(i) + ")");
+        if (v->offsets[m] > v->bytes_len) return fail(RH_ERR_ARG, "VARBYTES: value offsets exceed bytes_len");
+        return RH_OK;
+    }
     void route(const uint8_t *keys, size_t m, std::vector<std::vector<uint32_t>> &rows) const {
         rows.assign(G, {});
         for (size_t i = 0; i < m; i++) rows[owner(keys + i * kl)].push_back((uint32_t)i);
@@ -577,7 +650,23 @@ struct rh_sstore {
             for (size_t i = 0; i < m; i++) memcpy(&dst[i * w], reinterpret_cast<const T *>(src) + (size_t)rows[i] * w, w * sizeof(T));
         };
         pick(p.keys, static_cast<const uint8_t *>(h.keys), kl);
-        pick(p.vals, static_cast<const uint8_t *>(h.values), vr);
+        if (var && !h.values) {
+            // a delete-only batch without values: the shard gets none either
+        } else if (var) {  // (offsets validated by the caller: check_var_offsets)
+            const rh_var_values &v = *static_cast<const rh_var_values *>(h.values);
+            p.is_var = true;
+            p.voffs.resize(m + 1);
+            uint64_t at = 0;
+            for (size_t i = 0; i < m; i++) p.voffs[i] = at, at += v.offsets[rows[i] + 1] - v.offsets[rows[i]];
+            p.voffs[m] = at;
+            p.vals.resize(at + 4);  // (never empty: the heap pointer stays non-NULL)
+            for (size_t i = 0; i < m; i++)
+                if (p.voffs[i + 1] > p.voffs[i])
+                    memcpy(&p.vals[p.voffs[i]], v.bytes + v.offsets[rows[i]], p.voffs[i + 1] - p.voffs[i]);
+            p.var = rh_var_values{p.vals.data(), p.voffs.data(), at};
+        } else {
+            pick(p.vals, static_cast<const uint8_t *>(h.values), vr);
+        }
         if (schema.record_kind != RH_REC_PLAIN) pick(p.tags, h.tags, 1);
         if (dated) {
             pick(p.phys, h.phys, 1);
@@ -1209,18 +1298,24 @@ int lock_sizes(rh_sstore *s, std::unique_lock<std::mutex> &g) {
     return st.rc ? fail(st.rc, st.msg) : RH_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int rh_sstore_create(const int *devices, int n, const rh_schema *schema, rh_sstore **out) {
+// rh_sstore_create (flags = 0) and rh_sstore_create_flags: every check before any device call
+int sstore_create(const int *devices, int n, const rh_schema *schema, uint32_t flags, rh_sstore **out) {
     if (!devices || n < 1 || n > 64 || !schema || !out) return fail(RH_ERR_ARG, "sstore: bad arguments");
-    // before any device call: a sharded load cuts fixed-width value rows per shard
-    if (schema->value_kind == RH_VAL_VARBYTES)
+    if (flags & ~RH_SSTORE_VARBYTES) return fail(RH_ERR_ARG, "sstore: unknown flag bit");
+    // without the flag a sharded load cuts fixed-width value rows per shard
+    const bool var = schema->value_kind == RH_VAL_VARBYTES;
+    if (var && !(flags & RH_SSTORE_VARBYTES))
         return fail(RH_ERR_UNSUPPORTED, "sstore: VARBYTES values are not supported by the sharded store (use one rh_store)");
+    if (var) {  // a device batch of such a map is routed on the GPU: the key kinds the route takes
+        const bool numeric = schema->key_kind == RH_KEY_U32 || schema->key_kind == RH_KEY_U64;
+        if (schema->key_kind == RH_KEY_UNIT || !rh::route_key_supported((uint32_t)key_row(*schema), numeric))
+            return fail(RH_ERR_UNSUPPORTED, "sstore: VARBYTES values need u32, u64, byte-row or string keys of 8, 16, 32 "
+                                            "or 64 bytes (the keys the route takes)");
+    }
     rh_sstore *s = new (std::nothrow) rh_sstore();
     if (!s) return fail(RH_ERR_OOM, "sstore: host allocation failed");
     s->schema = *schema;
+    s->var = var;
     s->G = n;
     s->kl = (size_t)key_row(*schema);
     s->shards.assign(n, nullptr);
@@ -1253,6 +1348,18 @@ int rh_sstore_create(const int *devices, int n, const rh_schema *schema, rh_ssto
     }
     *out = s;
     return RH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rh_sstore_create(const int *devices, int n, const rh_schema *schema, rh_sstore **out) {
+    return sstore_create(devices, n, schema, 0, out);
+}
+
+int rh_sstore_create_flags(const int *devices, int n, const rh_schema *schema, uint32_t flags, rh_sstore **out) {
+    return sstore_create(devices, n, schema, flags, out);
 }
 
 int rh_sstore_destroy(rh_sstore *s) {
@@ -1295,9 +1402,11 @@ int rh_sstore_set_splitters(rh_sstore *s, const void *keys) {
 int rh_sstore_load(rh_sstore *s, const rh_columns *h, size_t n) {
     if (!s || !h) return fail(RH_ERR_ARG, "NULL");
     if (n && s->kl && !h->keys) return fail(RH_ERR_ARG, "keys column is NULL");
+    if (n && s->var && !h->values) return fail(RH_ERR_ARG, "values column is NULL");
     if (int rc = rh::check_str_rows(s->schema, h->keys, n)) return rc;
     std::lock_guard<std::mutex> g(s->mu);
     const int G = s->G;
+    std::vector<rh_var_values> vdesc(s->var ? G : 0);  // shard j's values: the caller's heap, its offsets from cut[j]
     const size_t kl = s->kl, vr = value_row(s->schema);
     const uint8_t *keys = static_cast<const uint8_t *>(h->keys);
     std::vector<uint64_t> cut(G + 1);
@@ -1325,7 +1434,11 @@ int rh_sstore_load(rh_sstore *s, const rh_columns *h, size_t n) {
         rc = fail(RH_ERR_ARG, "keys must be strictly increasing (sorted, no duplicates)");
     } else {
         rc = s->each(s->all(), [&](int j) -> int {
-            const rh_columns c = part(j);
+            rh_columns c = part(j);
+            if (s->var && h->values) {
+                vdesc[j] = var_from(h->values, cut[j]);
+                c.values = &vdesc[j];
+            }
             return rh_store_load(s->shards[j], &c, cut[j + 1] - cut[j]);
         });
     }
@@ -1367,6 +1480,13 @@ int rh_sstore_stage(rh_sstore *s, const rh_columns *h, const uint8_t *ops, size_
         s->changed();
         return RH_OK;
     }
+    if (s->var) {  // (a delete-only batch may leave the values out, as for one store)
+        if (h->values) {
+            if ((rc = rh_sstore::check_var_offsets(*h, m))) return rc;
+        } else if (std::find(ops, ops + m, uint8_t(0)) != ops + m) {
+            return fail(RH_ERR_ARG, "values column is NULL");
+        }
+    }
     try {
         std::vector<std::vector<uint32_t>> rows;
         s->route(keys, m, rows);
@@ -1407,6 +1527,7 @@ int rh_sstore_apply(rh_sstore *s, const rh_columns *h, const uint8_t *ops, size_
         if (sc.value_kind != RH_VAL_UNIT && !h->values) return fail(RH_ERR_ARG, "values column is NULL");
         if (sc.record_kind == RH_REC_DATED && (!h->phys || !h->logical || !h->node))
             return fail(RH_ERR_ARG, "DATED records need phys / logical / node columns");
+        if (s->var && (rc = rh_sstore::check_var_offsets(*h, m))) return rc;
     }
     uint64_t c[64][3] = {};
     try {
@@ -1486,6 +1607,7 @@ int load_device_locked(rh_sstore *s, int device, const rh_columns &cols, size_t 
     std::fill(s->dirty.begin(), s->dirty.end(), 0);
     // edge[j]: the rows cut[j] - 1 and cut[j] (the second alone when cut[j] is 0)
     std::vector<uint8_t> edge((size_t)G * 2 * kl + 1, 0);
+    std::vector<rh_var_values> vdesc(s->var ? G : 0);  // VARBYTES: each shard's view of the value column
     auto run = [&]() -> int {
         if (int rc = stg->open(device)) return rc;
         SS_HIP(hipEventRecord(stg->ev, producer));  // the caller's columns are whole once this has happened
@@ -1513,8 +1635,12 @@ int load_device_locked(rh_sstore *s, int device, const rh_columns &cols, size_t 
             rh_columns view;
             const uint8_t *ops;
             void *after;
-            if (int rc = s->shard_view(j, device, columns_from(s->schema, cols, cut[j]), nullptr, rows, stg->ev,
-                                       after_stream, &view, &ops, &after))
+            rh_columns from = columns_from(s->schema, cols, cut[j]);
+            if (s->var) {  // the same heap, the offsets from the cut on: read in place on `device`
+                vdesc[j] = var_from(cols.values, cut[j]);
+                from.values = &vdesc[j];
+            }
+            if (int rc = s->shard_view(j, device, from, nullptr, rows, stg->ev, after_stream, &view, &ops, &after))
                 return rc;
             return rh_store_load_device(s->shards[j], &view, rows, after);
         });
@@ -1543,6 +1669,8 @@ int check_device_columns(const rh_sstore *s, const rh_columns *c, size_t n) {
     if (sc.value_kind != RH_VAL_UNIT && !c->values) return fail(RH_ERR_ARG, "values column is NULL");
     if (sc.record_kind == RH_REC_DATED && (!c->phys || !c->logical || !c->node))
         return fail(RH_ERR_ARG, "DATED records need phys / logical / node columns");
+    if (s->var && !static_cast<const rh_var_values *>(c->values)->offsets)
+        return fail(RH_ERR_ARG, "VARBYTES: the value offsets are NULL");
     return RH_OK;
 }
 
@@ -1577,12 +1705,21 @@ int rh_sstore_apply_device(rh_sstore *s, int device, const rh_columns *dev_cols,
         if ((rc = stg->ensure(device, s->schema, cap))) return rc;
         SS_HIP(hipEventRecord(stg->ev, static_cast<hipStream_t>(after_stream)));
         SS_HIP(hipStreamWaitEvent(stg->st, stg->ev, 0));
-        const rh_columns out = stg->cols(0, in);
+        rh_columns out = stg->cols(0, in);
         uint8_t *ops_out = dev_ops ? static_cast<uint8_t *>(stg->p[ColBuf::OPS]) : nullptr;
-        uint64_t cnt[64], start[64];
-        if ((rc = rh_route_columns_device(&s->schema, s->split.data(), G, &in, dev_ops, m, &out, ops_out, stg->cap, cnt,
-                                          start, stg->st)))
-            return rc;
+        uint64_t cnt[64], start[64], heap_bytes = 0;
+        std::vector<rh_var_values> vdesc(s->var ? G : 0);  // VARBYTES: each shard's segment of the routed value column
+        if (s->var) {
+            // the routed heap holds at most the batch's own heap (well-formed offsets), so that is its room
+            if ((rc = stg->ensure_heap(static_cast<const rh_var_values *>(in.values)->bytes_len))) return rc;
+            out.values = stg->var_view(0);
+            rc = rh_route_columns_var_device(&s->schema, s->split.data(), G, &in, dev_ops, m, &out, ops_out, stg->cap, cnt,
+                                             start, &heap_bytes, stg->st);
+        } else {
+            rc = rh_route_columns_device(&s->schema, s->split.data(), G, &in, dev_ops, m, &out, ops_out, stg->cap, cnt, start,
+                                         stg->st);
+        }
+        if (rc) return rc;
         std::vector<int> idx;
         for (int t = 0; t < G; t++) {
             if (!cnt[t]) continue;
@@ -1598,8 +1735,13 @@ int rh_sstore_apply_device(rh_sstore *s, int device, const rh_columns *dev_cols,
             rh_columns view;
             const uint8_t *ops;
             void *after;
-            if (int q = s->shard_view(t, device, stg->cols(start[t], in), ops_out ? ops_out + start[t] : nullptr, cnt[t],
-                                      stg->ev, stg->st, &view, &ops, &after))
+            rh_columns seg = stg->cols(start[t], in);
+            if (s->var) {  // {bytes, offsets + starts[t], bytes_len}: a valid value column as it is
+                vdesc[t] = rh_var_values{stg->heap, stg->voff + start[t], stg->heap_cap};
+                seg.values = &vdesc[t];
+            }
+            if (int q = s->shard_view(t, device, seg, ops_out ? ops_out + start[t] : nullptr, cnt[t], stg->ev, stg->st, &view,
+                                      &ops, &after))
                 return q;
             return rh_store_apply_device(s->shards[t], &view, ops, cnt[t], &c[t][0], &c[t][1], &c[t][2], after);
         });
@@ -1669,7 +1811,11 @@ int rh_sstore_load_snapshot(rh_sstore *dated, rh_sstore *proj, int key_form, con
     rh_schema ds = a->schema;
     ds.record_kind = RH_REC_DATED;
     if ((rc = stg->ensure(device, ds, std::max<size_t>(n, 1)))) return rc;
-    const rh_columns cols = stg->all(0);
+    rh_columns cols = stg->all(0);
+    if (a->var) {  // the values of a file of len bytes fit in a heap of roundup4(len)
+        if ((rc = stg->ensure_heap(std::max<size_t>(len, 4)))) return rc;
+        cols.values = stg->var_view(0);
+    }
     rh_snapshot_info inf{};
     if ((rc = rh_snapshot_decode_device(&ds, key_form, dev_bytes, len, &cols, stg->cap, &inf, stg->st))) return rc;
     // FileSnapshot::save writes the map's iteration, so the keys increase strictly; any other file

@@ -22,16 +22,15 @@
 // the LDS window and out[0 .. total).
 #include "snap_encode.hpp"
 
+#include "byte_window.hpp"
+
 namespace rh {
 
 namespace {
 
 constexpr uint32_t ENC_BLOCK = 256;   // entries per workgroup
-constexpr uint32_t ENC_WIN = 32768;   // bytes of one LDS window (a multiple of 512)
-constexpr uint32_t ENC_DIRECT = 256;  // a value's part of a window of at least this many bytes skips the LDS
-constexpr uint32_t ENC_GROUP = 8;     // lanes that copy one shorter part: a wave works on 64 / ENC_GROUP values at a time
-constexpr uint32_t ENC_BATCH = ENC_DIRECT / 4 / ENC_GROUP;  // words per lane that cover such a part
-constexpr uint32_t ENC_LDS = ENC_WIN + ENC_WIN / 16 / 8;  // the window, and a bit per 16-byte granule of it
+// the window and the value copies are byte_window.hpp's (shared with the ragged route, shard_route.hip)
+constexpr uint32_t ENC_WIN = BW_WIN, ENC_DIRECT = BW_DIRECT, ENC_GROUP = BW_GROUP, ENC_LDS = BW_LDS;
 constexpr uint64_t ENC_SUM_TILE = 4096;
 
 // a string key's length: the row's last byte, clipped as the lift clips it
@@ -103,9 +102,7 @@ __global__ __launch_bounds__(256) void k_enc_sum(const uint64_t *tomb, uint64_t 
     if (threadIdx.x == 0 && part[0]) atomicAdd(total, part[0]);
 }
 
-__device__ inline uint64_t shfl64(uint64_t v, int k) {
-    return ((uint64_t)__shfl((uint32_t)(v >> 32), k) << 32) | __shfl((uint32_t)v, k);
-}
+__device__ inline uint64_t shfl64(uint64_t v, int k) { return bw_shfl64(v, k); }
 
 // the low nb bytes of v to win[r ..), the bytes that fall outside the window dropped
 __device__ inline void enc_put(uint8_t *win, int32_t r, uint32_t v, uint32_t nb) {
@@ -120,64 +117,17 @@ __device__ inline void enc_put64(uint8_t *win, int32_t r, uint64_t v) {
 __device__ inline uint32_t enc_left(uint32_t klen, uint32_t j) { return klen > j ? (klen - j < 4 ? klen - j : 4u) : 0u; }
 
 // Bytes [S, S + N) of the value column to win[R .. R + N) (inside the window, N < ENC_DIRECT), by
-// ENC_GROUP lanes.  The whole words of the window inside the range are each one load from the
-// source, at whatever alignment that has there, and one LDS store -- a lane's loads all issued
-// before its first store, so a part costs one memory latency, not one per step; the at most 3
-// bytes before and behind them go byte by byte.  Every read lies inside [S, S + N).
+// ENC_GROUP lanes (bw_copy).  Every read lies inside [S, S + N).
 __device__ inline void enc_copy(const EncCols &c, uint8_t *win, uint64_t S, uint32_t R, uint32_t N, uint32_t sub) {
-    const uint8_t *src = c.values + S;
-    const uint32_t pre = (4u - (R & 3u)) & 3u, head = pre < N ? pre : N;
-    const uint32_t nw = (N - head) >> 2, tail = N - head - 4 * nw;  // nw < ENC_BATCH * ENC_GROUP
-    uint32_t *dst = reinterpret_cast<uint32_t *>(win + R + head);
-    uint32_t v[ENC_BATCH];
-#pragma unroll
-    for (uint32_t u = 0; u < ENC_BATCH; u++) {
-        const uint32_t j = sub + u * ENC_GROUP;
-        v[u] = 0;
-        if (j < nw) __builtin_memcpy(&v[u], src + head + 4 * j, 4);
-    }
-#pragma unroll
-    for (uint32_t u = 0; u < ENC_BATCH; u++) {
-        const uint32_t j = sub + u * ENC_GROUP;
-        if (j < nw) dst[j] = v[u];
-    }
-    static_assert(ENC_GROUP >= 3, "one lane per edge byte");
-    if (sub < head) win[R + sub] = src[sub];
-    if (sub < tail) win[R + head + 4 * nw + sub] = src[head + 4 * nw + sub];
+    bw_copy(c.values + S, win, R, N, sub);
 }
 
-// A long part of a value (N >= ENC_DIRECT), by the whole wave, straight to the file: its whole
-// 16-byte granules (all this value's, so all this workgroup's) are loaded from the source at
-// whatever alignment it has and stored aligned -- 16 bytes a lane, four granules a lane in flight,
-// 4 KiB a step -- and marked in `direct` so that the stream-out leaves them alone; the at most
-// 15 + 15 bytes before and behind them take the window like a short part.  File offset of the
-// part: w + R (w a multiple of 16).
+// A long part of a value (N >= ENC_DIRECT), by the whole wave, straight to the file (bw_direct: its
+// whole 16-byte granules are all this value's, so all this workgroup's).  File offset of the part:
+// w + R (w a multiple of 16).
 __device__ inline void enc_direct(const EncCols &c, uint8_t *win, uint32_t *direct, uint8_t *out, uint64_t w,
                                   uint64_t S, uint32_t R, uint32_t N, uint32_t lane) {
-    const uint32_t head = (16u - (R & 15u)) & 15u;
-    const uint32_t G = (N - head) / 16, tail = N - head - 16 * G, g0 = (R + head) / 16;
-    const uint8_t *src = c.values + S + head;
-    uint4 *dst = reinterpret_cast<uint4 *>(out + w) + g0;
-    for (uint32_t g = lane; g < G; g += 256) {
-        uint4 v[4];
-#pragma unroll
-        for (uint32_t u = 0; u < 4; u++) {
-            v[u] = make_uint4(0, 0, 0, 0);
-            if (g + 64 * u < G) __builtin_memcpy(&v[u], src + 16ull * (g + 64 * u), 16);
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < 4; u++) {
-            const uint32_t gg = g + 64 * u;
-            if (gg < G) {
-                dst[gg] = v[u];
-                atomicOr(&direct[(g0 + gg) >> 5], 1u << ((g0 + gg) & 31));
-            }
-        }
-    }
-    if (lane < ENC_GROUP) {
-        if (head) enc_copy(c, win, S, R, head, lane);
-        if (tail) enc_copy(c, win, S + head + 16ull * G, R + head + 16 * G, tail, lane);
-    }
+    bw_direct(c.values + S, win, direct, out + w, R, N, lane);
 }
 
 __global__ __launch_bounds__(256) void k_enc_write(RagFmt f, EncCols c, uint64_t n, const uint64_t *start, uint8_t *out) {

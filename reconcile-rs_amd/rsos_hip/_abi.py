@@ -20,6 +20,7 @@ REC_PLAIN, REC_DATED, REC_PROJECTION = 0, 1, 2
 BLOCK, SUPER = 256, 65536
 FORM_ARRAY, FORM_VEC = 0, 1  # rh_key_form: [u8; L] | Vec<u8> / String
 FORM_RAGGED = 2  # flag OR-ed with either: the byte-granular locate (string keys, VARBYTES values)
+SSTORE_VARBYTES = 1  # rh_sstore_create_flags: the sharded map takes VARBYTES values
 
 
 class Schema(C.Structure):
@@ -133,6 +134,8 @@ SIGNATURES = [
     ("rh_estore_fingerprints", C.c_int, [P, C.c_uint64, C.c_uint64, U8P]),
     ("rh_estore_set_host_tier", C.c_int, [P, C.c_int]),
     ("rh_sstore_create", C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(Schema), C.POINTER(C.c_void_p)]),
+    ("rh_sstore_create_flags", C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(Schema), C.c_uint32,
+                                         C.POINTER(C.c_void_p)]),
     ("rh_sstore_destroy", C.c_int, [P]),
     ("rh_sstore_shard_count", C.c_int, [P]),
     ("rh_sstore_shard", C.c_int, [P, C.c_int, C.POINTER(C.c_void_p)]),
@@ -148,6 +151,8 @@ SIGNATURES = [
     ("rh_sstore_load_snapshot", C.c_int, [P, P, C.c_int, VP, SZ, C.c_int, C.c_int, C.POINTER(SnapshotInfo)]),
     ("rh_route_columns_device", C.c_int, [C.POINTER(Schema), VP, C.c_int, C.POINTER(Columns), U8P, SZ,
                                           C.POINTER(Columns), U8P, SZ, U64P, U64P, VP]),
+    ("rh_route_columns_var_device", C.c_int, [C.POINTER(Schema), VP, C.c_int, C.POINTER(Columns), U8P, SZ,
+                                              C.POINTER(Columns), U8P, SZ, U64P, U64P, C.POINTER(C.c_uint64), VP]),
     ("rh_sstore_len", C.c_int, [P, C.POINTER(C.c_uint64)]),
     ("rh_sstore_aggregates", C.c_int, [P, U64P, U64P, SZ, P]),
     ("rh_sstore_aggregate_keys", C.c_int, [P, C.c_int, VP, C.c_int, VP, C.POINTER(Aggregate)]),

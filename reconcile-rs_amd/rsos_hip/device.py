@@ -132,6 +132,55 @@ def route_columns(schema: RecordSchema, splitters, shards: int, cols: Dict[str, 
     return out, ops_out, counts[:shards], starts[:shards]
 
 
+def route_columns_var(schema: RecordSchema, splitters, shards: int, cols: Dict[str, torch.Tensor],
+                      ops: Optional[torch.Tensor] = None, out: Optional[Dict[str, torch.Tensor]] = None,
+                      ops_out: Optional[torch.Tensor] = None, cap_rows: Optional[int] = None,
+                      heap_cap: Optional[int] = None):
+    """route_columns for a 'var' schema (rh_route_columns_var_device): the same row partition, and the
+    values -- `values` the uint8 heap, `value_offsets` n + 1 offsets -- packed in output-row order into
+    out['values'] (a heap of `heap_cap` bytes, a multiple of 4; default: the input heap's size rounded
+    up to 4, which always suffices for well-formed offsets) with out['value_offsets'][0 .. R] written,
+    R = starts[-1] + roundup16(counts[-1]).  Shard s's values are the heap with the offsets from
+    starts[s] on.  Returns (out columns, out ops, counts, starts, heap_bytes).  A fixed-width schema
+    goes to route_columns' entry point unchanged (heap_bytes = 0)."""
+    import numpy as np
+    n = _check_cols(schema, cols)
+    if ops is not None and (ops.numel() != n or not ops.is_cuda):
+        raise ValueError("ops must be n device bytes")
+    dev = next(iter(cols.values())).device
+    if cap_rows is None:
+        cap_rows = n + 16 * max(shards, 0)
+    if out is None:
+        out = {k: torch.empty((cap_rows,) + tuple(v.shape[1:]), dtype=v.dtype, device=dev)
+               for k, v in cols.items() if v is not None and not (schema.is_var and k in ("values", VAR_OFFSETS))}
+        if schema.is_var:
+            if heap_cap is None:
+                heap_cap = (cols["values"].numel() + 3) // 4 * 4
+            out["values"] = torch.empty(max(heap_cap, 4), dtype=torch.uint8, device=dev)
+            out[VAR_OFFSETS] = torch.empty(cap_rows + 1, dtype=cols[VAR_OFFSETS].dtype, device=dev)
+    if ops is not None and ops_out is None:
+        ops_out = torch.empty(cap_rows, dtype=torch.uint8, device=dev)
+    sp = np.ascontiguousarray(splitters, dtype=np.uint8).reshape(-1)
+    counts, starts = np.zeros(max(shards, 1), np.uint64), np.zeros(max(shards, 1), np.uint64)
+    heap_bytes = C.c_uint64(0)
+    s, cin = schema.c(), _columns(cols)
+    if schema.is_var:  # the output heap is handed over as it is: its capacity, never a padded copy
+        if heap_cap is None:
+            heap_cap = out["values"].numel() // 4 * 4
+        if out["values"].numel() < heap_cap or out[VAR_OFFSETS].numel() < cap_rows + 1:
+            raise ValueError("out['values'] / out['value_offsets'] are smaller than heap_cap / cap_rows + 1")
+        cout = A.Columns(*[_ptr(out.get(k)) for k in COLS])
+        var = A.VarValues(_ptr(out["values"]), _ptr(out[VAR_OFFSETS]), heap_cap)
+        cout.values = C.addressof(var)
+    else:
+        cout = _columns(out)
+    A.check(A.lib().rh_route_columns_var_device(C.byref(s), sp.ctypes.data if sp.size else None, shards, C.byref(cin),
+                                                _ptr(ops), n, C.byref(cout), _ptr(ops_out), cap_rows,
+                                                counts.ctypes.data, starts.ctypes.data, C.byref(heap_bytes), _stream()),
+            "rh_route_columns_var_device")
+    return out, ops_out, counts[:shards], starts[:shards], int(heap_bytes.value)
+
+
 def lift_records(schema: RecordSchema, cols: Dict[str, torch.Tensor], block_sums: bool = True,
                  fps: Optional[torch.Tensor] = None, bsums: Optional[torch.Tensor] = None
                  ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:

@@ -54,14 +54,21 @@ class _Shard(GpuFingerprintStore):
 class ShardedStore(GpuFingerprintStore):
     _P = "rh_sstore_"
 
-    def __init__(self, schema: RecordSchema, devices: Sequence[int], host_tier: Optional[bool] = None):
+    def __init__(self, schema: RecordSchema, devices: Sequence[int], host_tier: Optional[bool] = None,
+                 var_values: bool = False):
+        """var_values=True opts in to a 'var' schema (String / Vec<u8> values: rh_sstore_create_flags with
+        RH_SSTORE_VARBYTES); without it such a schema is refused, as ever."""
         if not devices:
             raise ValueError("at least one device")
         self.schema = schema
         self._s = schema.c()
         devs = (C.c_int * len(devices))(*devices)
         h = C.c_void_p()
-        A.check(A.lib().rh_sstore_create(devs, len(devices), C.byref(self._s), C.byref(h)), "rh_sstore_create")
+        if var_values:
+            A.check(A.lib().rh_sstore_create_flags(devs, len(devices), C.byref(self._s), A.SSTORE_VARBYTES, C.byref(h)),
+                    "rh_sstore_create_flags")
+        else:
+            A.check(A.lib().rh_sstore_create(devs, len(devices), C.byref(self._s), C.byref(h)), "rh_sstore_create")
         self._h = h
         self.shards = []
         for i in range(len(devices)):

@@ -122,6 +122,8 @@ pub const RH_FORM_VEC: c_int = 1;
 /// Flag OR-ed with `RH_FORM_ARRAY` / `RH_FORM_VEC`: the byte-granular snapshot locate, which
 /// `RH_KEY_STR` stores (`RH_FORM_VEC | RH_FORM_RAGGED`) and `RH_VAL_VARBYTES` schemas need.
 pub const RH_FORM_RAGGED: c_int = 2;
+/// `rh_sstore_create_flags`: the sharded map takes `RH_VAL_VARBYTES` values (`String` / `Vec<u8>`).
+pub const RH_SSTORE_VARBYTES: u32 = 1;
 
 // Every entry point of include/rsos_hip.h, in header order.
 extern "C" {
@@ -224,6 +226,8 @@ extern "C" {
     pub fn rh_estore_fingerprints(store: *mut rh_estore, lo: u64, hi: u64, host_out: *mut u8) -> c_int;
     pub fn rh_estore_set_host_tier(store: *mut rh_estore, enable: c_int) -> c_int;
     pub fn rh_sstore_create(devices: *const c_int, n: c_int, schema: *const rh_schema, out: *mut *mut rh_sstore) -> c_int;
+    pub fn rh_sstore_create_flags(devices: *const c_int, n: c_int, schema: *const rh_schema, flags: u32,
+                                  out: *mut *mut rh_sstore) -> c_int;
     pub fn rh_sstore_destroy(store: *mut rh_sstore) -> c_int;
     pub fn rh_sstore_shard_count(store: *mut rh_sstore) -> c_int;
     pub fn rh_sstore_shard(store: *mut rh_sstore, i: c_int, out: *mut *mut rh_store) -> c_int;
@@ -245,6 +249,11 @@ extern "C" {
                                    dev_in: *const rh_columns, dev_ops_in: *const u8, n: usize,
                                    dev_out: *const rh_columns, dev_ops_out: *mut u8, cap_rows: usize,
                                    counts: *mut u64, starts: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn rh_route_columns_var_device(schema: *const rh_schema, host_splitters: *const c_void, shards: c_int,
+                                       dev_in: *const rh_columns, dev_ops_in: *const u8, n: usize,
+                                       dev_out: *const rh_columns, dev_ops_out: *mut u8, cap_rows: usize,
+                                       counts: *mut u64, starts: *mut u64, heap_bytes: *mut u64,
+                                       stream: *mut c_void) -> c_int;
     pub fn rh_sstore_len(store: *mut rh_sstore, out: *mut u64) -> c_int;
     pub fn rh_sstore_aggregates(store: *mut rh_sstore, lo: *const u64, hi: *const u64, r: usize,
                                 out: *mut rh_aggregate) -> c_int;

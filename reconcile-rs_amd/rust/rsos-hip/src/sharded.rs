@@ -11,7 +11,9 @@
 //! protocol round's segments inside one shard are that shard's own round and the few that
 //! straddle a boundary are resolved from their two boundary shards.  `ShortString<W>` keys with `()`,
 //! `u32` / `i32` or `u64` / `i64` values are sharded like any byte rows of width W (the default cut
-//! uses the leading 8 bytes; each shard lifts the strings); `String` / `Vec<u8>` values are not.  The host keeps `K` and `V`
+//! uses the leading 8 bytes; each shard lifts the strings); `String` / `Vec<u8>` values are sharded too
+//! (`rh_sstore_create_flags` with `RH_SSTORE_VARBYTES`: a load hands each shard the batch's heap with
+//! its own slice of the offsets, a batch's values are packed per shard).  The host keeps `K` and `V`
 //! in its own rank-ordered index, as `HipFingerprintMap` does; every fingerprint is the GPU lift.
 
 use std::ops::{Bound, RangeBounds};
@@ -67,9 +69,11 @@ impl<K: GpuKey, V: GpuRecord> HipShardedMap<K, V> {
         assert!(!devices.is_empty(), "rsos-hip: a sharded map needs at least one device");
         let mut p = std::ptr::null_mut();
         let s = schema::<K, V>();
+        // `String` / `Vec<u8>` values (VARBYTES) are opt-in at the C boundary: the flag selects them
+        let flags = if s.value_kind == ffi::RH_VAL_VARBYTES { ffi::RH_SSTORE_VARBYTES } else { 0 };
         // SAFETY: valid device array, schema and out-pointer.
-        check(unsafe { ffi::rh_sstore_create(devices.as_ptr(), devices.len() as c_int, &s, &mut p) },
-              "rh_sstore_create");
+        check(unsafe { ffi::rh_sstore_create_flags(devices.as_ptr(), devices.len() as c_int, &s, flags, &mut p) },
+              "rh_sstore_create_flags");
         let store = ShardedHandle(p);
         // SAFETY: store was just created.
         check(unsafe { ffi::rh_sstore_set_host_tier(store.0, 1, 0) }, "rh_sstore_set_host_tier");
