@@ -116,7 +116,10 @@ __device__ __forceinline__ RoundSeg round_decide(uint64_t l, uint64_t h, const u
     else if (span == 1) k = 2, st = 1;
     else {
         k = 2;
-        st = sqrt_policy ? (uint64_t)__fsqrt_rn((float)span) : (span + b - 1) / b;
+        // sqrtf: the correctly rounded root (the reference's f32::sqrt is IEEE).  __fsqrt_rn is the
+        // native 1-ULP v_sqrt_f32 here, whose truncation differs from the reference's on 27,041 of the
+        // spans within 16 float32 steps of a square, the smallest 16,793,602 (profiles/sqrt_stride_sweep.json)
+        st = sqrt_policy ? (uint64_t)sqrtf((float)span) : (span + b - 1) / b;
         if (st == 0) st = 1;  // SplitStride::per_child
     }
     if (k == 2 && span > 1 && st >= span) k = 1;

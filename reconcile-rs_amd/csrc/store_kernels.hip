@@ -704,7 +704,7 @@ __global__ void k_bounds(const uint8_t *keys, uint64_t n, const uint8_t *lo_key,
 // (Σ new entries' contrib − Σ replaced entries' contrib, mod 2^256)
 // 512-row workgroups (~2,000 partials per 1 M batch): at 1,024 lanes the 256-bit accumulators
 // of the totals spilled to scratch (a 128-VGPR cap)
-constexpr int DB_PARTS = 7, DB_WG = 512, DP_WG = 512, PU = 8;
+constexpr int DB_PARTS = 7, PU = 8;  // DB_WG, DP_WG: store_kernels.hpp
 
 __global__ __launch_bounds__(DB_WG) void k_delta_build(const uint8_t *sfps, const uint8_t *sops, uint64_t m,
                                                      const uint32_t *rank_b, const uint8_t *present_b,

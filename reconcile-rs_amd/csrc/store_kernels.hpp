@@ -12,6 +12,10 @@
 
 namespace rh {
 
+// workgroup sizes of the delta-run kernels (k_delta_build and its partials' pass k_delta_parts,
+// store_kernels.hip): here so that tests/device_units.hip instantiates acc_block_reduce at them
+constexpr int DB_WG = 512, DP_WG = 512;
+
 // Growable device scratch buffers in numbered slots, reused across calls.  Growing a slot
 // drains `stream` first, so no in-flight kernel still reads the freed buffer.
 struct Scratch {
