@@ -72,6 +72,95 @@ __device__ __forceinline__ void compress(uint32_t cv[8], const uint32_t m[16], u
 }
 #undef RH_G
 
+// The same compression with the wave's issue priority following the instruction class
+// (profiles/r07_micro_valu_rule.log).  gfx950 issues v_add3_u32 and
+// v_alignbit_b32 at one per ~4.2 cycles per SIMD and v_xor_b32 / v_add_u32 at one per ~2.1,
+// and a SIMD whose waves all have one priority serves them oldest first, so a mixed stream
+// runs at the slow rate throughout (~3.9).  With s_setprio raised over each run of slow
+// instructions, a wave in a fast run issues in the shadow of another wave's slow instruction
+// and the mix runs at ~2.3 cycles per instruction.  The four G of a column or diagonal step
+// are therefore written phase by phase, 4 or 8 instructions of one class at a time, and the
+// order is pinned with sched_barrier: the compiler's own schedule mixes the classes.
+#define RH_SLOW()                              \
+    do {                                       \
+        __builtin_amdgcn_sched_barrier(0);     \
+        __builtin_amdgcn_s_setprio(1);         \
+        __builtin_amdgcn_sched_barrier(0);     \
+    } while (0)
+#define RH_FAST()                              \
+    do {                                       \
+        __builtin_amdgcn_sched_barrier(0);     \
+        __builtin_amdgcn_s_setprio(0);         \
+        __builtin_amdgcn_sched_barrier(0);     \
+    } while (0)
+// four independent G: (a_i, b_i, c_i, d_i) with message words (x_i, y_i); entered and left
+// at the raised priority (the last rotates run on into the next step's v_add3)
+#define RH_G4(a0, b0, c0, d0, x0, y0, a1, b1, c1, d1, x1, y1, a2, b2, c2, d2, x2, y2, a3, b3, c3, d3, x3, y3) \
+    do {                                                                                                  \
+        a0 = a0 + b0 + (x0); a1 = a1 + b1 + (x1); a2 = a2 + b2 + (x2); a3 = a3 + b3 + (x3);               \
+        RH_FAST();                                                                                        \
+        d0 ^= a0; d1 ^= a1; d2 ^= a2; d3 ^= a3;                                                           \
+        RH_SLOW();                                                                                        \
+        d0 = rotr(d0, 16); d1 = rotr(d1, 16); d2 = rotr(d2, 16); d3 = rotr(d3, 16);                       \
+        RH_FAST();                                                                                        \
+        c0 += d0; c1 += d1; c2 += d2; c3 += d3;                                                           \
+        b0 ^= c0; b1 ^= c1; b2 ^= c2; b3 ^= c3;                                                           \
+        RH_SLOW();                                                                                        \
+        b0 = rotr(b0, 12); b1 = rotr(b1, 12); b2 = rotr(b2, 12); b3 = rotr(b3, 12);                       \
+        a0 = a0 + b0 + (y0); a1 = a1 + b1 + (y1); a2 = a2 + b2 + (y2); a3 = a3 + b3 + (y3);               \
+        RH_FAST();                                                                                        \
+        d0 ^= a0; d1 ^= a1; d2 ^= a2; d3 ^= a3;                                                           \
+        RH_SLOW();                                                                                        \
+        d0 = rotr(d0, 8); d1 = rotr(d1, 8); d2 = rotr(d2, 8); d3 = rotr(d3, 8);                           \
+        RH_FAST();                                                                                        \
+        c0 += d0; c1 += d1; c2 += d2; c3 += d3;                                                           \
+        b0 ^= c0; b1 ^= c1; b2 ^= c2; b3 ^= c3;                                                           \
+        RH_SLOW();                                                                                        \
+        b0 = rotr(b0, 7); b1 = rotr(b1, 7); b2 = rotr(b2, 7); b3 = rotr(b3, 7);                           \
+    } while (0)
+
+__device__ __forceinline__ void compress_prio(uint32_t cv[8], const uint32_t m[16], uint32_t counter_lo,
+                                              uint32_t counter_hi, uint32_t block_len, uint32_t flags) {
+    uint32_t v0 = cv[0], v1 = cv[1], v2 = cv[2], v3 = cv[3];
+    uint32_t v4 = cv[4], v5 = cv[5], v6 = cv[6], v7 = cv[7];
+    uint32_t v8 = IV0, v9 = IV1, v10 = IV2, v11 = IV3;
+    uint32_t v12 = counter_lo, v13 = counter_hi, v14 = block_len, v15 = flags;
+#define RH_ROUND(s0, s1, s2, s3, s4, s5, s6, s7, s8, s9, s10, s11, s12, s13, s14, s15)              \
+    RH_G4(v0, v4, v8, v12, m[s0], m[s1], v1, v5, v9, v13, m[s2], m[s3],                            \
+          v2, v6, v10, v14, m[s4], m[s5], v3, v7, v11, v15, m[s6], m[s7]);                         \
+    RH_G4(v0, v5, v10, v15, m[s8], m[s9], v1, v6, v11, v12, m[s10], m[s11],                        \
+          v2, v7, v8, v13, m[s12], m[s13], v3, v4, v9, v14, m[s14], m[s15]);
+    RH_SLOW();
+    RH_ROUND(0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
+    RH_ROUND(2, 6, 3, 10, 7, 0, 4, 13, 1, 11, 12, 5, 9, 14, 15, 8);
+    RH_ROUND(3, 4, 10, 12, 13, 2, 7, 14, 6, 5, 9, 0, 11, 15, 8, 1);
+    RH_ROUND(10, 7, 12, 9, 14, 3, 13, 15, 4, 0, 11, 2, 5, 8, 1, 6);
+    RH_ROUND(12, 13, 9, 11, 15, 10, 14, 8, 7, 2, 5, 3, 0, 1, 6, 4);
+    RH_ROUND(9, 14, 11, 5, 8, 12, 15, 1, 13, 3, 0, 10, 2, 6, 4, 7);
+    RH_ROUND(11, 15, 5, 0, 1, 9, 8, 6, 14, 10, 2, 12, 3, 4, 7, 13);
+#undef RH_ROUND
+    RH_FAST();
+    cv[0] = v0 ^ v8;
+    cv[1] = v1 ^ v9;
+    cv[2] = v2 ^ v10;
+    cv[3] = v3 ^ v11;
+    cv[4] = v4 ^ v12;
+    cv[5] = v5 ^ v13;
+    cv[6] = v6 ^ v14;
+    cv[7] = v7 ^ v15;
+}
+#undef RH_G4
+#undef RH_SLOW
+#undef RH_FAST
+
+// PRIO selects compress_prio; every caller but k_lift's small-record path takes the plain one
+template <bool PRIO>
+__device__ __forceinline__ void compress_as(uint32_t cv[8], const uint32_t m[16], uint32_t counter_lo,
+                                            uint32_t counter_hi, uint32_t block_len, uint32_t flags) {
+    if constexpr (PRIO) compress_prio(cv, m, counter_lo, counter_hi, block_len, flags);
+    else compress(cv, m, counter_lo, counter_hi, block_len, flags);
+}
+
 __device__ __forceinline__ void cv_iv(uint32_t cv[8]) {
     cv[0] = IV0; cv[1] = IV1; cv[2] = IV2; cv[3] = IV3;
     cv[4] = IV4; cv[5] = IV5; cv[6] = IV6; cv[7] = IV7;

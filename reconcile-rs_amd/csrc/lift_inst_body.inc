@@ -4,6 +4,8 @@
 // lift_<shape>.hip after defining RH_NAME, RH_KK, RH_KL, RH_VK, RH_VL.
 #include <hip/hip_ext.h>
 
+#include <cstdlib>
+
 #include "internal.hpp"
 #include "lift_kernels.hpp"
 #include "snap_lift.hpp"
@@ -15,6 +17,22 @@
 
 namespace rh {
 
+// k_lift in the form the launch asks for: Layout::SMALL shapes (the whole message in registers)
+// have a second instantiation that compresses with compress_prio; streamed shapes have one form
+template <int RK, bool T, bool D>
+static void RH_CAT(lift_form_, RH_NAME)(bool prio, dim3 grid, dim3 block, hipStream_t st, const DevCols &c, uint64_t n,
+                                        uint8_t *fps, uint8_t *bsums, uint8_t *fps2, uint8_t *bsums2) {
+    if constexpr (Layout<RH_KK, RH_KL, RH_VK, RH_VL, RK>::SMALL) {
+        if (prio) {
+            hipLaunchKernelGGL((k_lift<RH_KK, RH_KL, RH_VK, RH_VL, RK, T, D, true>), grid, block, 0, st, c, n, fps, bsums,
+                               fps2, bsums2);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((k_lift<RH_KK, RH_KL, RH_VK, RH_VL, RK, T, D, false>), grid, block, 0, st, c, n, fps, bsums, fps2,
+                       bsums2);
+}
+
 hipError_t RH_CAT(launch_lift_, RH_NAME)(int rk, bool tags, bool dual, const DevCols &c, uint64_t n,
                                          uint8_t *fps, uint8_t *bsums, uint8_t *fps2,
                                          uint8_t *bsums2, hipStream_t st) {
@@ -22,8 +40,10 @@ hipError_t RH_CAT(launch_lift_, RH_NAME)(int rk, bool tags, bool dual, const Dev
     if (n == 0) return hipSuccess;
     const uint64_t nblk = (n + LIFT_THREADS - 1) / LIFT_THREADS;
     const dim3 grid((uint32_t)nblk), block(LIFT_THREADS);
-#define RH_L(RK, T, D) \
-    hipLaunchKernelGGL((k_lift<RH_KK, RH_KL, RH_VK, RH_VL, RK, T, D>), grid, block, 0, st, c, n, fps, bsums, fps2, bsums2)
+    // read at every launch, so one process can run both forms (RSOS_HIP_LIFT_PRIO=0: the plain compression)
+    const char *form = getenv("RSOS_HIP_LIFT_PRIO");
+    const bool prio = !(form && *form == '0');
+#define RH_L(RK, T, D) RH_CAT(lift_form_, RH_NAME)<RK, T, D>(prio, grid, block, st, c, n, fps, bsums, fps2, bsums2)
     if (dual) {
         if (tags) RH_L(REC_DATED, true, true);
         else RH_L(REC_DATED, false, true);

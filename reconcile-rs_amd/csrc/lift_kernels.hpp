@@ -138,7 +138,9 @@ __device__ __forceinline__ void build_prefix(const uint32_t *kw, const uint32_t 
 }
 
 // ---- hashing: whole message in registers (LEN <= 1024) -----------------------------------
-template <int LEN>
+// PRIO: the compression that raises the wave's priority over its half-rate instructions
+// (compress_prio); only k_lift's whole-message path asks for it
+template <int LEN, bool PRIO = false>
 __device__ __forceinline__ void hash_words(const uint32_t *w, uint32_t out[8]) {
     constexpr int NW = LEN / 4;
     constexpr int NB = LEN == 0 ? 1 : (LEN + 63) / 64;
@@ -151,7 +153,7 @@ __device__ __forceinline__ void hash_words(const uint32_t *w, uint32_t out[8]) {
         for (int j = 0; j < 16; j++) m[j] = (16 * b + j < NW) ? w[16 * b + j] : 0u;
         const uint32_t flags = (b == 0 ? CHUNK_START : 0) | (b == NB - 1 ? (CHUNK_END | ROOT) : 0);
         const uint32_t blen = (b == NB - 1) ? (uint32_t)(LEN - 64 * b) : 64u;
-        compress(out, m, 0, 0, blen, flags);
+        compress_as<PRIO>(out, m, 0, 0, blen, flags);
     }
 }
 
@@ -265,14 +267,14 @@ struct Streamer {
 };
 
 // lift of one present record of layout L (prefix words built, value row pointer given)
-template <class L>
+template <class L, bool PRIO = false>
 __device__ __forceinline__ void hash_present(const uint32_t *pw, const uint8_t *vrow, uint32_t out[8]) {
     if constexpr (L::SMALL) {
         uint32_t w[L::LEN / 4 > 0 ? L::LEN / 4 : 1];
 #pragma unroll
         for (int j = 0; j < L::PW; j++) w[j] = pw[j];
         if constexpr (L::VW > 0) ldw<L::VW, L::ROW_ALIGN>(vrow, w + L::PW);
-        hash_words<L::LEN>(w, out);
+        hash_words<L::LEN, PRIO>(w, out);
     } else {
         Streamer<L> s{pw, vrow};
         s.run(out);
@@ -297,7 +299,7 @@ __device__ __forceinline__ void store_sum(uint8_t *dst, uint64_t g, const uint32
 // one block-0 compression whose words, length and flags are chosen per lane; only present
 // lanes go on to the value blocks.  A wave mixing both kinds then runs NB compressions, not
 // NB + 1 as two divergent paths would.
-template <class L, int KK, int RK>
+template <class L, int KK, int RK, bool PRIO = false>
 __device__ __forceinline__ void hash_merged(const uint32_t *kw, const uint32_t *sw, bool tomb, const uint8_t *vrow,
                                             uint32_t h[8]) {
     constexpr int NW = L::LEN / 4, NB = (L::LEN + 63) / 64, TW = L::LEN_TOMB / 4;
@@ -314,7 +316,7 @@ __device__ __forceinline__ void hash_merged(const uint32_t *kw, const uint32_t *
     cv_iv(h);
     const uint32_t blen0 = tomb ? (uint32_t)L::LEN_TOMB : (uint32_t)(NB == 1 ? L::LEN : 64);
     const uint32_t fl0 = CHUNK_START | ((tomb || NB == 1) ? (CHUNK_END | ROOT) : 0u);
-    compress(h, m, 0, 0, blen0, fl0);
+    compress_as<PRIO>(h, m, 0, 0, blen0, fl0);
     if (!tomb) {
 #pragma unroll
         for (int b = 1; b < NB; b++) {
@@ -322,7 +324,7 @@ __device__ __forceinline__ void hash_merged(const uint32_t *kw, const uint32_t *
             for (int j = 0; j < 16; j++) m[j] = (16 * b + j < NW) ? w[16 * b + j] : 0u;
             const uint32_t flags = b == NB - 1 ? (CHUNK_END | ROOT) : 0u;
             const uint32_t blen = b == NB - 1 ? (uint32_t)(L::LEN - 64 * b) : 64u;
-            compress(h, m, 0, 0, blen, flags);
+            compress_as<PRIO>(h, m, 0, 0, blen, flags);
         }
     }
 }
@@ -334,41 +336,46 @@ struct LayoutAligned : L {
 };
 
 // lift one record (present or tombstone) of layout L; TAGS: tomb varies per lane
-template <class L, int KK, int RK, bool TAGS>
+template <class L, int KK, int RK, bool TAGS, bool PRIO = false>
 __device__ __forceinline__ void lift_record_l(const uint32_t *kw, const uint32_t *sw, bool tomb,
                                               const uint8_t *vrow, uint32_t h[8]) {
     if constexpr (TAGS && RK != REC_PLAIN && L::SMALL && L::LEN_TOMB <= 64) {
-        hash_merged<L, KK, RK>(kw, sw, tomb, vrow, h);
+        hash_merged<L, KK, RK, PRIO>(kw, sw, tomb, vrow, h);
     } else if (RK != REC_PLAIN && tomb) {
         constexpr int TW = L::LEN_TOMB / 4;
         uint32_t w[TW];
         build_prefix<L, KK, RK>(kw, sw, true, w);
-        hash_words<L::LEN_TOMB>(w, h);
+        hash_words<L::LEN_TOMB, PRIO>(w, h);
     } else {
         uint32_t pw[L::PW > 0 ? L::PW : 1];
         build_prefix<L, KK, RK>(kw, sw, false, pw);
-        hash_present<L>(pw, vrow, h);
+        hash_present<L, PRIO>(pw, vrow, h);
     }
 }
 
 // lift one record (present or tombstone) of schema (KK,KL,VK,VL,RK); TAGS: tomb varies per lane
-template <int KK, int KL, int VK, int VL, int RK, bool TAGS = true>
+template <int KK, int KL, int VK, int VL, int RK, bool TAGS = true, bool PRIO = false>
 __device__ __forceinline__ void lift_record(const uint32_t *kw, const uint32_t *sw, bool tomb,
                                             const uint8_t *vrow, uint32_t h[8]) {
-    lift_record_l<Layout<KK, KL, VK, VL, RK>, KK, RK, TAGS>(kw, sw, tomb, vrow, h);
+    lift_record_l<Layout<KK, KL, VK, VL, RK>, KK, RK, TAGS, PRIO>(kw, sw, tomb, vrow, h);
 }
 
 constexpr int LIFT_THREADS = 256;
 
 // The lift kernel.  DUAL: RK == DATED, and additionally emit the projection fingerprint
 // lift(k, State<V>) from the same loaded record (Replica::map_insert's second lift).
-template <int KK, int KL, int VK, int VL, int RK, bool TAGS, bool DUAL>
+// PRIO: the whole-message path compresses with compress_prio (launch_lift_* chooses it for
+// Layout::SMALL shapes unless RSOS_HIP_LIFT_PRIO=0); the bytes written are the same.
+template <int KK, int KL, int VK, int VL, int RK, bool TAGS, bool DUAL, bool PRIO = false>
 __global__ __launch_bounds__(LIFT_THREADS) void k_lift(DevCols c, uint64_t n, uint8_t *fps,
                                                        uint8_t *bsums, uint8_t *fps2,
                                                        uint8_t *bsums2) {
     using L = Layout<KK, KL, VK, VL, RK>;
     static_assert(LIFT_THREADS == 256, "block_sum_fps256");
     __shared__ SumTile tile;
+    // a new wave is the youngest on its SIMD and would issue its loads behind every hashing wave:
+    // it starts above them (compress_prio then moves between 1 and 0); 3.07 -> 2.93 ms per 100 M
+    if constexpr (PRIO) __builtin_amdgcn_s_setprio(2);
     const uint64_t i = (uint64_t)blockIdx.x * LIFT_THREADS + threadIdx.x;
     const bool valid = i < n;
     uint32_t h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -391,7 +398,7 @@ __global__ __launch_bounds__(LIFT_THREADS) void k_lift(DevCols c, uint64_t n, ui
         if constexpr (RK == REC_DATED) load_stamp(cb, t, sw);
         const bool tomb = TAGS ? (cb.tags[t] != 0) : false;
         const uint8_t *vrow = cb.values + t * (uint32_t)L::VAL_ROW;
-        lift_record<KK, KL, VK, VL, RK, TAGS>(kw, sw, tomb, vrow, h);
+        lift_record<KK, KL, VK, VL, RK, TAGS, PRIO>(kw, sw, tomb, vrow, h);
         if (c.dst) {
             // bounded: a bucket the key sort could not order leaves its rows' slots unwritten
             // (the sort flags it and the batch is sorted and lifted again)
@@ -401,7 +408,7 @@ __global__ __launch_bounds__(LIFT_THREADS) void k_lift(DevCols c, uint64_t n, ui
             store_fp(fps + b0 * 32, t, h);
         }
         if constexpr (DUAL) {
-            lift_record<KK, KL, VK, VL, REC_PROJECTION, TAGS>(kw, sw, tomb, vrow, h2);
+            lift_record<KK, KL, VK, VL, REC_PROJECTION, TAGS, PRIO>(kw, sw, tomb, vrow, h2);
             store_fp(fps2 + b0 * 32, t, h2);
         }
     }
