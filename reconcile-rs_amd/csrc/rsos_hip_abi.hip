@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/rsos_hip.h"
+#include "abi_error.hpp"
 #include "internal.hpp"
 #include "host_tier.hpp"
 #include "lift_kernels.hpp"

@@ -27,12 +27,11 @@
 #include <vector>
 
 #include "../../include/rsos_hip.h"
+#include "abi_error.hpp"
 #include "byte_window.hpp"
 #include "shard_route.hpp"
 
 namespace rh {
-int set_error(int code, const std::string &msg);  // rsos_hip_abi.hip
-int check_schema_arg(const rh_schema *s);         // check_schema: RH_ERR_ARG naming the bad field
 
 namespace {
 

@@ -35,22 +35,10 @@
 #include <vector>
 
 #include "../../include/rsos_hip.h"
+#include "abi_error.hpp"
 #include "internal.hpp"
 #include "round_decide.hpp"
 #include "shard_route.hpp"
-
-namespace rh {
-int set_error(int code, const std::string &msg);  // rsos_hip_abi.hip: the calling thread's rh_last_error
-bool debug_fail_point(const char *name);          // rh_debug_fail_point, armed on the calling thread
-// host key rows of a RH_KEY_STR schema (length byte, zero padding), RH_ERR_ARG naming the first bad
-// row; RH_OK for every other key kind.  Checked here for the whole batch before any shard changes
-int check_str_rows(const rh_schema &s, const void *keys, size_t n);
-// rh_store_protocol_round in two halves (rsos_hip_abi.hip round_entry): a device round issued
-// (*pending: the store stays locked) and completed later on the same thread
-int store_round_issue(rh_store *s, int policy, uint64_t fan_out, const rh_segments *active, rh_segments *children,
-                      rh_segments *enumerations, rh_round_outcome *outcome, bool *pending);
-int store_round_complete(rh_store *s, rh_segments *children, rh_segments *enumerations, rh_round_outcome *outcome);
-}
 
 namespace {
 

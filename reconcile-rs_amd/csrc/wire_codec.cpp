@@ -12,10 +12,7 @@
 #include <string>
 
 #include "../../include/rsos_hip.h"
-
-namespace rh {
-int set_error(int code, const std::string &msg);  // rsos_hip_abi.hip
-}
+#include "abi_error.hpp"
 
 namespace {
 

@@ -126,6 +126,45 @@ def test_fixed_lift_rejects_short_buffer(rsos_hip_lib):
     assert rc == A.ERR_ARG and b"exceeds" in A.lib().rh_last_error()
 
 
+def test_last_error_is_shared_by_every_source(rsos_hip_lib):
+    """The thread's error string has one definition (csrc/rsos_hip_abi.hip): an entry point of each source
+    file of the library, refused on an argument check before any HIP call, leaves its own message for
+    rh_last_error; a thread that made no failing call reads an empty string."""
+    import threading
+    from rsos_hip import _abi as A
+    L = A.lib()
+    good = A.Schema(A.KEY_U32, 4, A.VAL_U32, 4, A.REC_PLAIN, 0)
+    bad_key, bad_value = A.Schema(9, 4, 1, 4, 0, 0), A.Schema(1, 4, 9, 4, 0, 0)
+    out, n64, buf = C.c_void_p(), C.c_uint64(), (C.c_uint64 * 8)()
+    one_device, r_out, consumed = (C.c_int * 1)(0), C.c_size_t(), C.c_size_t()
+    calls = [  # (source file, call, status, a piece of its message)
+        ("rsos_hip_abi.hip (store)", lambda: L.rh_store_create(0, C.byref(bad_key), C.byref(out)), A.ERR_ARG,
+         b"bad key_kind"),
+        ("rsos_hip_abi.hip (estore)", lambda: L.rh_estore_create(0, None), A.ERR_ARG, b"out is NULL"),
+        ("rsos_hip_abi.hip (snapshot)", lambda: L.rh_snapshot_header(C.addressof(buf), 4, C.byref(n64)), A.ERR_DATA,
+         b"shorter than the 8-byte format header"),
+        ("rsos_hip_abi.hip (lift)", lambda: L.rh_lift_encoded_async(C.addressof(buf), 7, C.addressof(buf), 1,
+                                                                    C.addressof(buf), None, None),
+         A.ERR_ARG, b"multiple of 4"),
+        ("sharded_store.hip", lambda: L.rh_sstore_create(one_device, 0, C.byref(good), C.byref(out)), A.ERR_ARG,
+         b"sstore: bad arguments"),
+        ("shard_route.hip", lambda: L.rh_route_columns_device(C.byref(bad_value), None, 1, None, None, 0, None, None, 0, None,
+                                                              None, None), A.ERR_ARG, b"bad value_kind"),
+        ("wire_codec.cpp", lambda: L.rh_wire_decode_range_aggregates(C.byref(good), A.FORM_ARRAY, -1, None, 8, 0, None, None,
+                                                                     None, None, None, C.byref(r_out), C.byref(consumed)),
+         A.ERR_ARG, b"input is NULL"),
+    ]
+    for source, call, status, piece in calls:
+        assert call() == status, source
+        assert piece in L.rh_last_error(), (source, L.rh_last_error())
+    seen = []
+    t = threading.Thread(target=lambda: seen.append(L.rh_last_error()))
+    t.start()
+    t.join()
+    assert seen == [b""]
+    assert b"input is NULL" in L.rh_last_error()  # and this thread's is still its own
+
+
 def test_product_fails_loudly_without_the_library(tmp_path):
     """No CPU fallback: with librsos_hip.so missing, the binding raises instead of computing."""
     import subprocess
