@@ -374,6 +374,50 @@ typedef struct rh_round_outcome { /* RoundOutcome (protocol.rs:135-142)         
 int rh_store_protocol_round(rh_store *store, int policy, uint64_t fan_out, const rh_segments *active,
                             rh_segments *children, rh_segments *enumerations, rh_round_outcome *outcome);
 
+/* ---- Enumerate, batched ---------------------------------------------------------------------
+ * Rsos::enumerate (rsos/src/rsos_trait.rs:73-83) for every IDLIST range of a round at once: the
+ * keys of the `enumeration_ranges` that protocol_round_with_policy returns (rbsr/src/protocol.rs),
+ * in one call and one device round trip, where a caller otherwise asks a rank and a key dump per
+ * range.  Per-key fingerprints or payloads are not part of the answer (the caller owns K and V).
+ * Input: `ranges` in the form rh_store_protocol_round writes its `enumerations` -- start kind 0 =
+ * Unbounded, 1 = Included(key); end kind 0 = Unbounded, 1 = Excluded(key); key rows of key_len bytes
+ * (RH_KEY_STR: padded rows, as everywhere); `aggregates` is ignored and may be NULL.  A bound kind
+ * above 1, or a NULL key array beside a bounded side, is RH_ERR_ARG before any device call (the rule
+ * of rh_store_resolve_segments).
+ * Per range j: first_ranks[j] is the raw_start rh_store_resolve_segments gives for the same segment
+ * (Unbounded: 0), and the range has max(raw_end - raw_start, 0) rows: an inverted or empty range has
+ * no rows and still reports its first rank.  Ranges may overlap, repeat and come in any order; each
+ * is answered on its own.
+ * One snapshot: staged rows are applied first, and every range is answered against the same state
+ * of the store (on rh_sstore, under the map's lock, as every call).
+ * No compaction: base + delta run are read in place, as rh_store_keys reads up to 2^22 rows.
+ * max_rows = 0 means 2^22; above 2^22 is RH_ERR_ARG.  Ranges that hold more than max_rows rows in all:
+ * RH_ERR_ARG, the message naming the total and the cap, with out->first_ranks, offsets, n and rows
+ * still filled and keys NULL (as rh_snapshot_encode_device reports the room it needs) -- the caller
+ * splits the request, or pages a huge range with rh_store_keys.  Every other error leaves *out zeroed.
+ * The output lives in a buffer of the store's own that no other call writes: valid until the next
+ * enumerate call, load or destroy on that store.  The children and enumerations of the preceding
+ * rh_store_protocol_round stay valid across the call, so `ranges` may be that round's `enumerations`
+ * struct itself.  On rh_sstore the output is the sharded store's own buffer, never a shard's.
+ * n = 0 answers rows = 0 with no device call; an empty store answers all zeros; a broken sharded map
+ * is RH_ERR_STATE.
+ * Host tier: the same answers; with a fresh tier and ranges->n <= round_max (whenever
+ * rh_store_resolve_segments would be) the call is answered on the host, no device round trip.
+ * Sharded map: a range inside one shard is that shard's range, a range that straddles splitters
+ * the concatenation, in shard order, of its pieces; first_ranks is a global rank; the shards are
+ * driven concurrently, as rounds are.  The answer equals, byte for byte, that of one rh_store holding
+ * the same map.                                                                                */
+typedef struct rh_enumerated {
+    const uint64_t *first_ranks; /* n entries: Rank(start) of range j (Unbounded: 0)              */
+    const uint64_t *offsets;     /* n + 1 entries, offsets[0] = 0: range j's keys are rows
+                                    [offsets[j], offsets[j + 1]) of `keys`                       */
+    const void     *keys;        /* rows * key_len bytes, key order inside a range               */
+    size_t          n;           /* ranges                                                       */
+    uint64_t        rows;        /* offsets[n]                                                   */
+} rh_enumerated;
+int rh_store_enumerate_segments(rh_store *store, const rh_segments *ranges, uint64_t max_rows,
+                                rh_enumerated *out);
+
 /* Host tier (the diff path is latency-bound).  enable = 1 keeps, next to the
  * HBM-resident store, a host copy of the keys in rank order and the exclusive prefix sums of the
  * per-row fingerprints (computed on the device from the GPU lift; (key_len + 32) B of page-locked
@@ -795,6 +839,10 @@ int rh_sstore_split_segments(rh_sstore *store, size_t m, const uint64_t *select_
                              const uint64_t *lo, const uint64_t *hi, rh_aggregate *out);
 int rh_sstore_protocol_round(rh_sstore *store, int policy, uint64_t fan_out, const rh_segments *active,
                              rh_segments *children, rh_segments *enumerations, rh_round_outcome *outcome);
+/* rh_store_enumerate_segments over the shards (its contract above): a straddling range's pieces
+ * in shard order, global first ranks, the output in the sharded store's own buffer              */
+int rh_sstore_enumerate_segments(rh_sstore *store, const rh_segments *ranges, uint64_t max_rows,
+                                 rh_enumerated *out);
 int rh_sstore_set_host_tier(rh_sstore *store, int enable, uint64_t round_max);
 int rh_sstore_set_tier_policy(rh_sstore *store, int keep_fresh);
 int rh_sstore_reserve(rh_sstore *store, uint64_t rows, uint64_t batch_rows);

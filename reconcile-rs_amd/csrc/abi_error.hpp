@@ -20,4 +20,10 @@ int check_str_rows(const rh_schema &s, const void *keys, size_t n);
 int store_round_issue(rh_store *s, int policy, uint64_t fan_out, const rh_segments *active, rh_segments *children,
                       rh_segments *enumerations, rh_round_outcome *outcome, bool *pending);
 int store_round_complete(rh_store *s, rh_segments *children, rh_segments *enumerations, rh_round_outcome *outcome);
+// what both enumerate entry points check before any device call: NULL arguments, the bound kinds and
+// key arrays (rh_store_resolve_segments' rule), max_rows (0 becomes 2^22, more is RH_ERR_ARG); *out zeroed
+int check_enumerate_args(const void *store, const rh_segments *ranges, uint64_t *max_rows, rh_enumerated *out);
+// rh_store_enumerate_segments for a shard: ranges that hold more than max_rows rows are no error
+// here -- *over = true, `out` filled without rows -- since the map weighs the shards' totals together
+int store_enumerate(rh_store *s, const rh_segments *ranges, uint64_t max_rows, rh_enumerated *out, bool *over);
 }  // namespace rh

@@ -184,4 +184,31 @@ hipError_t launch_round_small(const uint32_t *rank, const RoundIn &in, const Rou
                               int sqrt_policy, uint64_t b, uint64_t cap, uint32_t kl, uint8_t *out, hipStream_t st);
 hipError_t launch_combine(const uint64_t *in, uint64_t parts, uint64_t r, uint64_t *out, hipStream_t st);
 
+// ---- Enumerate for many key ranges at once (enumerate_kernels.hip; rh_store_enumerate_segments) ----
+// The answer for r ranges, read back in one copy: first ranks (r u64), offsets (r + 1 u64), then,
+// 16-byte aligned, the rows (offsets[r] * key_len bytes)
+struct EnumLayout {
+    uint64_t first, offs, keys;
+};
+__host__ __device__ inline EnumLayout enum_layout(uint64_t r) {
+    return EnumLayout{0, 8 * r, (8 * (2 * r + 1) + 15) & ~15ull};
+}
+// every range's first view rank and row count (cnt: r + 1 entries, the last 0) from its bound keys'
+// searched ranks (rank_b in the base, rank_j in the delta run: row 2 j the start key's, 2 j + 1 the
+// end key's; sk / ek the bound kinds), and over a delta run (run.n > 0) its places (place[4 j ..]:
+// start b, start j, end b, end j).  run.nb: the base rows, with or without a run
+hipError_t launch_enum_plan(const uint32_t *rank_b, const uint32_t *rank_j, const uint8_t *sk, const uint8_t *ek,
+                            const RoundRun &run, uint64_t r, uint64_t *first, uint64_t *cnt, uint64_t *place,
+                            hipStream_t st);
+// the rows: output row t of range j (offs[j] <= t < offs[j + 1]) = view key first[j] + t - offs[j],
+// kl bytes each, tiled over the output rows.  Nothing is written when offs[r] > limit; `rows` sizes
+// the grid (the total if known, else limit)
+hipError_t launch_enum_emit(const uint64_t *first, const uint64_t *offs, const uint64_t *place, uint64_t r,
+                            const RoundRun &run, const uint8_t *bkeys, uint32_t kl, uint64_t limit, uint64_t rows,
+                            uint8_t *out, hipStream_t st);
+// hdr (first ranks and offsets, enum_layout's first `keys` bytes) and, unless offs[r] > limit, the
+// rows, into dst: mapped page-locked memory in enum_layout, as launch_copy_to_host stores
+hipError_t launch_enum_copy_out(const uint8_t *hdr, const uint8_t *keys, uint64_t r, uint32_t kl, uint64_t limit,
+                                uint64_t rows, uint8_t *dst, hipStream_t st);
+
 }  // namespace rh

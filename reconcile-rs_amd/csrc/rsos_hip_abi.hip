@@ -3061,6 +3061,17 @@ struct rh_store {
     DevBuf<uint8_t> q_in, q_res;
     static size_t pad8(size_t x) { return (x + 7) & ~size_t(7); }
     static size_t pad16(size_t x) { return (x + 15) & ~size_t(15); }
+    // r segments' bounds as one run of 2 r search keys, then the kinds (at kb = pad8(2 r kl): r start
+    // kinds, r end kinds): row 2j the start key, 2j + 1 the end key (unbounded: zeros)
+    void stage_bounds(uint8_t *h, size_t kb, size_t r, const uint8_t *sk, const uint8_t *skeys, const uint8_t *ek,
+                      const uint8_t *ekeys) const {
+        for (size_t j = 0; j < r; j++) {
+            if (sk[j]) memcpy(h + 2 * j * kl, skeys + j * kl, kl); else memset(h + 2 * j * kl, 0, kl);
+            if (ek[j]) memcpy(h + (2 * j + 1) * kl, ekeys + j * kl, kl); else memset(h + (2 * j + 1) * kl, 0, kl);
+        }
+        memcpy(h + kb, sk, r);
+        memcpy(h + kb + r, ek, r);
+    }
     // step 1, results in stage_out: lo[r] u64, hi[r] u64, aggregates[r]
     int resolve_staged(size_t r, const uint8_t *sk, const uint8_t *skeys, const uint8_t *ek, const uint8_t *ekeys,
                        const uint64_t **lo, const uint64_t **hi, const rh_aggregate **aggs) {
@@ -3072,12 +3083,7 @@ struct rh_store {
         stage_in.resize(in_bytes);
         stage_out.resize(out_bytes);
         uint8_t *h = stage_in.data();
-        for (size_t j = 0; j < r; j++) {  // row 2j: start key, 2j + 1: end key (unbounded: zeros)
-            if (sk[j]) memcpy(h + 2 * j * kl, skeys + j * kl, kl); else memset(h + 2 * j * kl, 0, kl);
-            if (ek[j]) memcpy(h + (2 * j + 1) * kl, ekeys + j * kl, kl); else memset(h + (2 * j + 1) * kl, 0, kl);
-        }
-        memcpy(h + kb, sk, r);
-        memcpy(h + kb + r, ek, r);
+        stage_bounds(h, kb, r, sk, skeys, ek, ekeys);
         RH_HIP(hipMemcpyAsync(q_in.p, h, in_bytes, hipMemcpyHostToDevice, stream));
         uint64_t *d_lo = reinterpret_cast<uint64_t *>(q_res.p), *d_hi = d_lo + r, *d_agg = d_hi + r;
         if (nb)
@@ -3160,6 +3166,120 @@ struct rh_store {
         if (m) memcpy(keys_out, keys, m * kl);
         if (q) memcpy(out, aggs, q * sizeof(rh_aggregate));
         return RH_OK;
+    }
+    // Enumerate for a round's IDLIST ranges at once (rh_store_enumerate_segments; Rsos::enumerate,
+    // rsos_trait.rs:73-83), over base + delta run as they stand: the bounds staged and searched as
+    // resolve_staged does (no range sums), then enumerate_kernels.hip's plan, the scan of the row
+    // counts, the emit and the copy out.  The answer lives in en_out, which nothing else writes (a
+    // round's outputs, in pr_out / stage_out / tier_out, stay as they are); the rows are emitted into
+    // the buffers the store already holds (en_rows rows) before the total is known, so a call whose
+    // rows fit makes one wait; one that outgrows them learns the total, grows them and emits again.
+    static constexpr uint64_t ENUM_MAX_ROWS = 1ull << 22;  // as KEYS_VIEW_MAX: no compaction below it
+    PinnedVec<uint8_t> en_in, en_out;
+    DevBuf<uint8_t> en_d, en_hdr, en_keys;  // bounds in; first ranks, offsets, counts, places; rows
+    uint64_t en_rows = 0;                   // rows en_keys and en_out have room for
+    uint64_t en_none[2] = {0, 0};           // the answer to no ranges (offsets[0] = 0)
+    void enumerated(size_t r, bool with_keys, rh_enumerated *out) {
+        const rh::EnumLayout L = rh::enum_layout(r);
+        const uint8_t *o = en_out.data();
+        const uint64_t *offs = reinterpret_cast<const uint64_t *>(o + L.offs);
+        *out = rh_enumerated{reinterpret_cast<const uint64_t *>(o + L.first), offs, with_keys ? o + L.keys : nullptr, r,
+                             offs[r]};
+    }
+    // *over: the ranges hold more than max_rows rows (first ranks, offsets and the total filled, no rows)
+    int enumerate_tier(const rh_segments &g, uint64_t max_rows, rh_enumerated *out, bool *over) {
+        const size_t r = g.n;
+        const rh::EnumLayout L = rh::enum_layout(r);
+        const uint8_t *sk = static_cast<const uint8_t *>(g.start_keys), *ek = static_cast<const uint8_t *>(g.end_keys);
+        en_out.resize(L.keys + 64);
+        uint64_t *first = reinterpret_cast<uint64_t *>(en_out.data() + L.first), total = 0;
+        for (size_t j = 0; j < r; j++) {
+            const uint64_t a = g.start_kinds[j] ? tier.lt(sk + j * kl).r : 0;
+            const uint64_t b = g.end_kinds[j] ? tier.lt(ek + j * kl).r : tier.n;
+            first[j] = a;
+            first[r + j] = total;  // offsets follow the first ranks
+            total += b > a ? b - a : 0;
+        }
+        first[2 * r] = total;
+        if ((*over = total > max_rows)) return enumerated(r, false, out), RH_OK;
+        en_out.resize(L.keys + total * kl + 64);  // (keeps what it holds)
+        first = reinterpret_cast<uint64_t *>(en_out.data() + L.first);
+        for (size_t j = 0; j < r; j++)
+            tier.copy_keys(first[j], first[j] + (first[r + j + 1] - first[r + j]), en_out.data() + L.keys + first[r + j] * kl);
+        return enumerated(r, true, out), RH_OK;
+    }
+    int enumerate_device(const rh_segments &g, uint64_t max_rows, rh_enumerated *out, bool *over) {
+        int rc;
+        const size_t r = g.n;
+        const rh::EnumLayout L = rh::enum_layout(r);
+        *over = false;
+        if (size() == 0) {  // nothing to search: all zeros
+            en_out.assign(L.keys + 64, 0);
+            return enumerated(r, true, out), RH_OK;
+        }
+        const uint8_t *skeys = static_cast<const uint8_t *>(g.start_keys), *ekeys = static_cast<const uint8_t *>(g.end_keys);
+        const size_t kb = pad8(2 * r * kl), in_bytes = kb + pad8(2 * r);
+        const size_t o_cnt = L.keys, o_place = o_cnt + 8 * (r + 1), hdr_bytes = o_place + 32 * r;
+        uint64_t room = std::min<uint64_t>(max_rows, std::max<uint64_t>(en_rows, 4096));
+        if ((rc = en_d.ensure(in_bytes + 64)) || (rc = en_hdr.ensure(hdr_bytes + 64)) ||
+            (rc = en_keys.ensure(room * kl + 64)) || (rc = q_rank.ensure(2 * r)) || (nd && (rc = q_drank.ensure(2 * r))))
+            return rc;
+        en_rows = std::max(en_rows, room);
+        en_in.resize(in_bytes);
+        en_out.clear();  // (a larger buffer need not keep the last answer)
+        en_out.resize(L.keys + room * kl + 64);
+        uint8_t *h = en_in.data();
+        stage_bounds(h, kb, r, g.start_kinds, skeys, g.end_kinds, ekeys);
+        RH_HIP(hipMemcpyAsync(en_d.p, h, in_bytes, hipMemcpyHostToDevice, stream));
+        if (nb)
+            RH_HIP(kops->search_sampled(bkeys[cb].p, nb, bsmp.p, bsmp2.p, en_d.p, 2 * r, q_rank.p, nullptr, stream,
+                                        base_table()));
+        else RH_HIP(hipMemsetAsync(q_rank.p, 0, 2 * r * 4, stream));
+        rh::RoundRun run{};
+        if (nd) {  // ranks in the run as well: view ranks and places
+            rh::RoundIn unused;
+            if ((rc = view_of(&run, &unused))) return rc;
+            RH_HIP(search_run(en_d.p, 2 * r, q_drank.p));
+        }
+        run.nb = nb;
+        auto hdr_at = [&](size_t o) { return reinterpret_cast<uint64_t *>(en_hdr.p + o); };
+        uint64_t *d_first = hdr_at(L.first), *d_offs = hdr_at(L.offs), *d_cnt = hdr_at(o_cnt), *d_place = hdr_at(o_place);
+        RH_HIP(rh::launch_enum_plan(q_rank.p, nd ? q_drank.p : nullptr, en_d.p + kb, en_d.p + kb + r, run, r, d_first, d_cnt,
+                                    d_place, stream));
+        RH_HIP(rh::launch_exclusive_scan_u64(d_cnt, d_offs, r + 1, scratch, stream));
+        // down in one layout: a kernel's stores into the mapped answer (the round path's choice), which
+        // reads the total on the device; without a device address, the header first, then the rows
+        uint8_t *mapped = nullptr;
+        const std::string keep = g_err;
+        if (dev_ptr(en_out, &mapped)) mapped = nullptr, g_err = keep;
+        const uint64_t *h_offs = reinterpret_cast<const uint64_t *>(en_out.data() + L.offs);
+        RH_HIP(rh::launch_enum_emit(d_first, d_offs, d_place, r, run, bkeys[cb].p, (uint32_t)kl, room, room, en_keys.p,
+                                    stream));
+        if (mapped) RH_HIP(rh::launch_enum_copy_out(en_hdr.p, en_keys.p, r, (uint32_t)kl, room, room, mapped, stream));
+        else RH_HIP(hipMemcpyAsync(en_out.data(), en_hdr.p, L.keys, hipMemcpyDeviceToHost, stream));
+        if ((rc = sync())) return rc;
+        const uint64_t total = h_offs[r];
+        if ((*over = total > max_rows)) return enumerated(r, false, out), RH_OK;
+        if (total > room) {  // (max_rows >= total > room: the buffers grow to the total, at most 2^22 rows)
+            if ((rc = en_keys.ensure(total * kl + 64))) return rc;
+            en_rows = room = total;
+            en_out.clear();
+            en_out.resize(L.keys + room * kl + 64);
+            if (mapped && dev_ptr(en_out, &mapped)) mapped = nullptr, g_err = keep;
+            RH_HIP(rh::launch_enum_emit(d_first, d_offs, d_place, r, run, bkeys[cb].p, (uint32_t)kl, room, total, en_keys.p,
+                                        stream));
+            if (mapped) {
+                RH_HIP(rh::launch_enum_copy_out(en_hdr.p, en_keys.p, r, (uint32_t)kl, room, total, mapped, stream));
+                if ((rc = sync())) return rc;
+                return enumerated(r, true, out), RH_OK;
+            }
+            RH_HIP(hipMemcpyAsync(en_out.data(), en_hdr.p, L.keys, hipMemcpyDeviceToHost, stream));
+        }
+        if (!mapped && total) {
+            RH_HIP(hipMemcpyAsync(en_out.data() + L.keys, en_keys.p, total * kl, hipMemcpyDeviceToHost, stream));
+            if ((rc = sync())) return rc;
+        }
+        return enumerated(r, true, out), RH_OK;
     }
     // A whole protocol round (protocol_round_with_policy, protocol.rs:212-317) for the policies
     // that decide on the span alone, in one device round trip, over the base run and any pending
@@ -3550,6 +3670,7 @@ struct rh_store {
         q_in.release(); q_res.release();
         stage_in.release(); stage_out.release(); stage_out2.release(); load_flag.release();
         r_in.release(); r_kind.release(); r_out.release(); r_seg.release(); r_part.release(); pr_out.release();
+        en_d.release(); en_hdr.release(); en_keys.release(); en_in.release(); en_out.release(); en_rows = 0;
         trs[0].release(); trs[1].release(); trun_keys.release();
         tsets[0].release(); tsets[1].release(); tier_dpre.release(); tier_spre.release(); tier_bpre.release(); tier_dsmp.release();
         if (cstream) (void)hipStreamDestroy(cstream);
@@ -3952,7 +4073,71 @@ int store_round_complete(rh_store *s, rh_segments *children, rh_segments *enumer
 }
 }  // namespace rh
 
+// rh_store_enumerate_segments.  *over (the sharded store's calls): more than max_rows rows is then
+// no error here -- *over = true, `out` filled without rows -- and the caller weighs its shards' totals
+static int enumerate_entry(rh_store *s, const rh_segments *ranges, uint64_t max_rows, rh_enumerated *out, bool *over) {
+    if (over) *over = false;
+    if (int rc = rh::check_enumerate_args(s, ranges, &max_rows, out)) return rc;
+    const size_t r = ranges->n;
+    std::lock_guard<std::mutex> g(s->mu);
+    if (r == 0) {  // no device call, not even for staged rows
+        *out = rh_enumerated{s->en_none, s->en_none, s->en_none, 0, 0};
+        return RH_OK;
+    }
+    bool ov = false;
+    int rc;
+    try {  // no exception crosses the C ABI
+        // staged rows first; then the host tier, whenever it would resolve these segments
+        const int t = s->tier_on && r <= s->tier_round_max ? tier_ready(s) : flush_locked(s);
+        if (t < 0) return t;
+        if (t) {
+            rc = s->enumerate_tier(*ranges, max_rows, out, &ov);
+        } else {
+            RH_HIP(hipSetDevice(s->device));
+            rc = s->enumerate_device(*ranges, max_rows, out, &ov);
+        }
+    } catch (const std::bad_alloc &) {
+        *out = rh_enumerated{};
+        return fail(RH_ERR_OOM, "enumerate: host allocation failed");
+    }
+    if (rc) {
+        *out = rh_enumerated{};
+        return rc;
+    }
+    if (over) *over = ov;
+    else if (ov)
+        return fail(RH_ERR_ARG, "enumerate: the ranges hold " + std::to_string(out->rows) + " rows, above max_rows = " +
+                                    std::to_string(max_rows) + " (split the request, or page a range with rh_store_keys)");
+    return RH_OK;
+}
+
+namespace rh {
+int check_enumerate_args(const void *store, const rh_segments *ranges, uint64_t *max_rows, rh_enumerated *out) {
+    if (!store || !ranges || !out) return fail(RH_ERR_ARG, "NULL");
+    *out = rh_enumerated{};
+    const size_t r = ranges->n;
+    if (r && (!ranges->start_kinds || !ranges->end_kinds)) return fail(RH_ERR_ARG, "ranges: NULL buffer");
+    for (size_t j = 0; j < r; j++) {
+        if (ranges->start_kinds[j] > 1 || ranges->end_kinds[j] > 1)
+            return fail(RH_ERR_ARG, "segment bound kind must be 0 (Unbounded) or 1 (Included / Excluded)");
+        if ((ranges->start_kinds[j] && !ranges->start_keys) || (ranges->end_kinds[j] && !ranges->end_keys))
+            return fail(RH_ERR_ARG, "bound key is NULL");
+    }
+    if (*max_rows > rh_store::ENUM_MAX_ROWS)
+        return fail(RH_ERR_ARG, "enumerate: max_rows above 2^22 (split the request, or page a range by rank)");
+    if (*max_rows == 0) *max_rows = rh_store::ENUM_MAX_ROWS;
+    return RH_OK;
+}
+int store_enumerate(rh_store *s, const rh_segments *ranges, uint64_t max_rows, rh_enumerated *out, bool *over) {
+    return enumerate_entry(s, ranges, max_rows, out, over);
+}
+}  // namespace rh
+
 extern "C" {
+
+int rh_store_enumerate_segments(rh_store *s, const rh_segments *ranges, uint64_t max_rows, rh_enumerated *out) {
+    return enumerate_entry(s, ranges, max_rows, out, nullptr);
+}
 
 int rh_store_fingerprints(rh_store *s, uint64_t lo, uint64_t hi, uint8_t *host_out) {
     if (!s) return fail(RH_ERR_ARG, "store is NULL");

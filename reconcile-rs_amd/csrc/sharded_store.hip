@@ -805,6 +805,85 @@ struct rh_sstore {
         return RH_OK;
     }
 
+    // ---- Enumerate over the shards (rh_sstore_enumerate_segments) ------------------------------
+    // Range j's keys lie in shards [a_j, b_j] (span): shard a_j answers from its start bound on, b_j
+    // up to its end bound, the shards between them whole; the pieces are concatenated in shard order,
+    // and the first rank is a_j's, made global.  a_j > b_j (empty or inverted): a_j is asked for the
+    // empty range at the start bound, which still gives the first rank.  Every shard holding a piece
+    // answers its pieces in one rh_store_enumerate_segments of its own, the shards concurrently; the
+    // answer is assembled in en_hdr / en_keys, this store's own (a shard's buffer is never handed out).
+    std::vector<uint64_t> en_hdr;  // first ranks (n), then offsets (n + 1)
+    std::vector<uint8_t> en_keys;
+    int enumerate(const rh_segments &g, uint64_t max_rows, rh_enumerated *out) {
+        const size_t r = g.n;
+        const uint8_t *skeys = static_cast<const uint8_t *>(g.start_keys), *ekeys = static_cast<const uint8_t *>(g.end_keys);
+        struct Job {
+            std::vector<uint8_t> sk, ek, skeys, ekeys;
+            std::vector<size_t> at;  // the range each piece belongs to
+            rh_enumerated got{};
+            bool over = false;
+        };
+        std::vector<Job> jobs(G);
+        std::vector<int> A(r);
+        auto add = [&](int s, size_t j, uint8_t skd, const uint8_t *skey, uint8_t ekd, const uint8_t *ekey) {
+            Job &q = jobs[s];
+            q.sk.push_back(skd), q.ek.push_back(ekd);
+            const size_t o = q.skeys.size();
+            q.skeys.resize(o + kl, 0), q.ekeys.resize(o + kl, 0);
+            if (skd) memcpy(q.skeys.data() + o, skey, kl);
+            if (ekd) memcpy(q.ekeys.data() + o, ekey, kl);
+            q.at.push_back(j);
+        };
+        for (size_t j = 0; j < r; j++) {
+            const uint8_t skd = g.start_kinds[j], ekd = g.end_kinds[j];
+            const uint8_t *skey = skd ? skeys + j * kl : nullptr, *ekey = ekd ? ekeys + j * kl : nullptr;
+            int b;
+            span(skd, skey, ekd, ekey, &A[j], &b);
+            if (A[j] > b) add(A[j], j, 1, skey, 1, skey);  // (an unbounded start has a_j = 0 <= b_j)
+            else
+                for (int s = A[j]; s <= b; s++) add(s, j, s == A[j] ? skd : 0, skey, s == b ? ekd : 0, ekey);
+        }
+        std::vector<int> idx;
+        for (int s = 0; s < G; s++)
+            if (!jobs[s].at.empty()) idx.push_back(s);
+        int rc = each(idx, [&](int s) -> int {
+            Job &q = jobs[s];
+            const rh_segments sub{q.sk.data(), q.skeys.data(), q.ek.data(), q.ekeys.data(), nullptr, q.at.size(), q.at.size()};
+            return rh::store_enumerate(shards[s], &sub, max_rows, &q.got, &q.over);
+        });
+        if (rc) return rc;
+        en_hdr.assign(2 * r + 1, 0);
+        uint64_t *first = en_hdr.data(), *offs = first + r;
+        for (int s : idx) {  // (a shard over the cap still reports its first ranks and offsets)
+            const Job &q = jobs[s];
+            for (size_t i = 0; i < q.at.size(); i++) {
+                const size_t j = q.at[i];
+                if (s == A[j]) first[j] = off[s] + q.got.first_ranks[i];
+                offs[j + 1] += q.got.offsets[i + 1] - q.got.offsets[i];
+            }
+        }
+        for (size_t j = 0; j < r; j++) offs[j + 1] += offs[j];
+        const uint64_t total = offs[r];
+        *out = rh_enumerated{first, offs, nullptr, r, total};
+        if (total > max_rows)
+            return fail(RH_ERR_ARG, "enumerate: the ranges hold " + std::to_string(total) + " rows, above max_rows = " +
+                                        std::to_string(max_rows) + " (split the request, or page a range with rh_sstore_keys)");
+        en_keys.resize(total * kl + 1);
+        std::vector<uint64_t> at(offs, offs + r);  // where each range's next piece goes: shard order
+        for (int s : idx) {
+            const Job &q = jobs[s];
+            for (size_t i = 0; i < q.at.size(); i++) {
+                const uint64_t rows = q.got.offsets[i + 1] - q.got.offsets[i];
+                if (rows)
+                    memcpy(en_keys.data() + at[q.at[i]] * kl, static_cast<const uint8_t *>(q.got.keys) + q.got.offsets[i] * kl,
+                           rows * kl);
+                at[q.at[i]] += rows;
+            }
+        }
+        out->keys = en_keys.data();
+        return RH_OK;
+    }
+
     // ---- a protocol round --------------------------------------------------------------------
     // One piece of the round's output: the children and enumerations of a run of segments, either
     // owned (copied) or borrowed from a shard's own round output (valid until that shard's next call)
@@ -2052,6 +2131,31 @@ int rh_sstore_protocol_round(rh_sstore *s, int policy, uint64_t fan_out, const r
         if (outcome) *outcome = rh_round_outcome{};
     }
     return rc;
+}
+
+int rh_sstore_enumerate_segments(rh_sstore *s, const rh_segments *ranges, uint64_t max_rows, rh_enumerated *out) {
+    if (int rc = rh::check_enumerate_args(s, ranges, &max_rows, out)) return rc;  // before any device call
+    const size_t r = ranges->n;
+    std::unique_lock<std::mutex> g;
+    if (r == 0) {  // no device call, not even for staged rows
+        g = std::unique_lock<std::mutex>(s->mu);
+        if (int rc = s->health()) return rc;
+        s->en_hdr.assign(1, 0);
+        *out = rh_enumerated{s->en_hdr.data(), s->en_hdr.data(), s->en_hdr.data(), 0, 0};
+        return RH_OK;
+    }
+    int rc = lock_sizes(s, g);
+    if (rc) return rc;
+    try {
+        rc = s->enumerate(*ranges, max_rows, out);
+    } catch (const std::bad_alloc &) {
+        *out = rh_enumerated{};
+        rc = fail(RH_ERR_OOM, "enumerate: host allocation failed");
+    } catch (...) {  // nothing crosses the C ABI
+        *out = rh_enumerated{};
+        rc = fail(RH_ERR_STATE, "enumerate: internal error");
+    }
+    return rc;  // (more rows than max_rows: RH_ERR_ARG with first ranks, offsets and the total filled)
 }
 
 int rh_sstore_set_host_tier(rh_sstore *s, int enable, uint64_t round_max) {

@@ -54,6 +54,14 @@ class RoundOutcome(C.Structure):  # rh_round_outcome
 POLICY_FIXED_FAN_OUT, POLICY_SQRT_FAN_OUT = 0, 1
 
 
+class Enumerated(C.Structure):  # rh_enumerated
+    _fields_ = [("first_ranks", C.c_void_p), ("offsets", C.c_void_p), ("keys", C.c_void_p), ("n", C.c_size_t),
+                ("rows", C.c_uint64)]
+
+
+ENUMERATE_MAX_ROWS = 1 << 22  # rh_store_enumerate_segments: max_rows 0 means this, more is refused
+
+
 class SnapshotInfo(C.Structure):
     _fields_ = [("entries", C.c_uint64), ("tombstones", C.c_uint64), ("entries_end", C.c_uint64),
                 ("keys", C.c_uint64)]
@@ -97,6 +105,7 @@ SIGNATURES = [
     ("rh_store_split_segments", C.c_int, [P, SZ, U64P, VP, SZ, U64P, U64P, P]),
     ("rh_store_protocol_round", C.c_int, [P, C.c_int, C.c_uint64, C.POINTER(Segments), C.POINTER(Segments),
                                           C.POINTER(Segments), C.POINTER(RoundOutcome)]),
+    ("rh_store_enumerate_segments", C.c_int, [P, C.POINTER(Segments), C.c_uint64, C.POINTER(Enumerated)]),
     ("rh_store_apply", C.c_int, [P, C.POINTER(Columns), U8P, SZ, C.POINTER(C.c_uint64),
                                  C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("rh_store_apply_device", C.c_int, [P, C.POINTER(Columns), U8P, SZ, C.POINTER(C.c_uint64),
@@ -165,6 +174,7 @@ SIGNATURES = [
     ("rh_sstore_split_segments", C.c_int, [P, SZ, U64P, VP, SZ, U64P, U64P, P]),
     ("rh_sstore_protocol_round", C.c_int, [P, C.c_int, C.c_uint64, C.POINTER(Segments), C.POINTER(Segments),
                                            C.POINTER(Segments), C.POINTER(RoundOutcome)]),
+    ("rh_sstore_enumerate_segments", C.c_int, [P, C.POINTER(Segments), C.c_uint64, C.POINTER(Enumerated)]),
     ("rh_sstore_set_host_tier", C.c_int, [P, C.c_int, C.c_uint64]),
     ("rh_sstore_set_tier_policy", C.c_int, [P, C.c_int]),
     ("rh_sstore_reserve", C.c_int, [P, C.c_uint64, C.c_uint64]),

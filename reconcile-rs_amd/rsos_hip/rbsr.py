@@ -286,6 +286,22 @@ def protocol_round_segments(store, policy, active,
                          int(oc.dropped_malformed)))
 
 
+def enumerate_ranges(store, enumeration_ranges, max_rows: int = 0) -> List[List[Key]]:
+    """The responder's IDLISTs for a round's enumeration ranges, one list of keys per range, in one
+    store call (rh_store_enumerate_segments) where Rsos::enumerate is asked range by range
+    (rsos_trait.rs:73-83).  `enumeration_ranges`: the (start, end) pairs protocol_round_with_policy
+    appends, or the Segments / RawSegments protocol_round_segments returns (a RawSegments is read in
+    place: the round's own output, before the store's next round)."""
+    if len(enumeration_ranges) == 0:
+        return []
+    _, offs, keys = store.enumerate_segments(enumeration_ranges, max_rows)
+    schema, o = store.schema, offs.tolist()
+    if schema.key_kind in (A.KEY_U32, A.KEY_U64):  # the rows are the integers, little-endian
+        ints = keys.view("<u4" if schema.key_kind == A.KEY_U32 else "<u8").reshape(-1).tolist()
+        return [ints[o[j]:o[j + 1]] for j in range(len(o) - 1)]
+    return [[_key_out(schema, keys[t].tobytes()) for t in range(o[j], o[j + 1])] for j in range(len(o) - 1)]
+
+
 def initial_segments(store) -> Segments:
     seg = Segments(store.schema.key_row, 1)
     agg = store.aggregate()

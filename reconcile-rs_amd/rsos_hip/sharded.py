@@ -18,6 +18,8 @@ no device-to-device traffic and one host thread per shard (include/rsos_hip.h, c
   protocol round        a run of segments inside one shard is that shard's own round; a segment
                         straddling a boundary is resolved from its two boundary shards, decided on
                         the host and cut by routed selects and rank-range aggregates
+  enumerate_segments    a range inside one shard is that shard's; one that straddles splitters is its
+                        pieces in shard order, first ranks made global (rh_sstore_enumerate_segments)
 
 ShardedStore has GpuFingerprintStore's interface (the same methods, on rh_sstore_* entry points), so
 rsos_hip.rbsr's native and two-call round paths run on it unchanged.

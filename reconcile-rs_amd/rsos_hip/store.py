@@ -366,6 +366,50 @@ class GpuFingerprintStore:
                                                 _np_ptr(hi_a), out), "rh_store_split_segments")
         return [self._key_out(keys[i].tobytes()) for i in range(m)], [Aggregate.from_c(out[j]) for j in range(q)]
 
+    # ---- Enumerate, batched (rh_store_enumerate_segments) ----------------------------------------
+    def enumerate_segments(self, segments, max_rows: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The keys of r key ranges in one call, against one state of the store: (first_ranks,
+        offsets, keys) -- first_ranks[j] = rank(start of range j) (Unbounded: 0), range j's keys are
+        rows offsets[j]:offsets[j + 1] of `keys` (uint8, rows x key_row), in key order; an empty or
+        inverted range has no rows.  `segments`: what resolve_segments takes (objects with .start /
+        .end, or (start, end) pairs; None = Unbounded, else Included(start) / Excluded(end)), or the
+        rbsr.Segments / RawSegments a protocol_round_segments returned as its enumerations.  The
+        arrays are copies.  Ranges holding more than max_rows rows (0: 2^22) raise RsosHipError, which
+        then carries first_ranks, offsets and rows (split the request, or page a range with keys)."""
+        kl = self.schema.key_row
+        if hasattr(segments, "c"):
+            cs = segments.c()
+        else:
+            r = len(segments)
+            sk, ek = np.zeros(max(r, 1), np.uint8), np.zeros(max(r, 1), np.uint8)
+            skeys, ekeys = np.zeros((max(r, 1), kl), np.uint8), np.zeros((max(r, 1), kl), np.uint8)
+            for j, seg in enumerate(segments):
+                start, end = (seg.start, seg.end) if hasattr(seg, "start") else seg
+                if start is not None:
+                    sk[j] = 1
+                    skeys[j] = np.frombuffer(self._key_bytes(start), np.uint8)
+                if end is not None:
+                    ek[j] = 1
+                    ekeys[j] = np.frombuffer(self._key_bytes(end), np.uint8)
+            cs = A.Segments(_np_ptr(sk), _np_ptr(skeys), _np_ptr(ek), _np_ptr(ekeys), None, r, max(r, 1))
+        out = A.Enumerated()
+        rc = self._f("enumerate_segments")(self._h, C.byref(cs), max_rows, C.byref(out))
+
+        def copied(ptr, shape, dtype) -> np.ndarray:
+            a = np.zeros(shape, dtype)
+            if a.nbytes and ptr:
+                C.memmove(a.ctypes.data, ptr, a.nbytes)
+            return a
+
+        n = int(out.n)
+        first, offs = copied(out.first_ranks, n, np.uint64), copied(out.offsets, n + 1, np.uint64)
+        if rc < 0:
+            err = A.RsosHipError(rc, self._P + "enumerate_segments", (A.lib().rh_last_error() or b"").decode())
+            if out.offsets:  # more rows than max_rows: the ranks, the offsets and the total still came back
+                err.first_ranks, err.offsets, err.rows = first, offs, int(out.rows)
+            raise err
+        return first, offs, copied(out.keys, (int(out.rows), kl), np.uint8)
+
     def apply(self, cols: Dict[str, np.ndarray], ops: np.ndarray) -> Tuple[int, int, int]:
         """Batched insert (op 0) / delete (op 1); returns (new, overwritten, deleted)."""
         c, held = self._host_columns(cols)

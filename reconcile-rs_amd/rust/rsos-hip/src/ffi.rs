@@ -111,6 +111,18 @@ pub struct rh_round_outcome {
     pub dropped_malformed: u64,
 }
 
+/// `rh_store_enumerate_segments` / `rh_sstore_enumerate_segments`: the keys of `n` key ranges, in the
+/// store's own buffer (valid until its next enumerate call, load or destroy).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct rh_enumerated {
+    pub first_ranks: *const u64,
+    pub offsets: *const u64,
+    pub keys: *const c_void,
+    pub n: usize,
+    pub rows: u64,
+}
+
 pub const RH_ERR_ARG: c_int = -1;
 pub const RH_ERR_HIP: c_int = -2;
 pub const RH_ERR_OOM: c_int = -3;
@@ -176,6 +188,8 @@ extern "C" {
     pub fn rh_store_protocol_round(store: *mut rh_store, policy: c_int, fan_out: u64, active: *const rh_segments,
                                    children: *mut rh_segments, enumerations: *mut rh_segments,
                                    outcome: *mut rh_round_outcome) -> c_int;
+    pub fn rh_store_enumerate_segments(store: *mut rh_store, ranges: *const rh_segments, max_rows: u64,
+                                       out: *mut rh_enumerated) -> c_int;
     pub fn rh_store_apply(store: *mut rh_store, cols: *const rh_columns, ops: *const u8, n: usize,
                           n_new: *mut u64, n_over: *mut u64, n_del: *mut u64) -> c_int;
     pub fn rh_store_apply_device(store: *mut rh_store, dev_cols: *const rh_columns, dev_ops: *const u8, n: usize,
@@ -272,6 +286,8 @@ extern "C" {
     pub fn rh_sstore_protocol_round(store: *mut rh_sstore, policy: c_int, fan_out: u64, active: *const rh_segments,
                                     children: *mut rh_segments, enumerations: *mut rh_segments,
                                     outcome: *mut rh_round_outcome) -> c_int;
+    pub fn rh_sstore_enumerate_segments(store: *mut rh_sstore, ranges: *const rh_segments, max_rows: u64,
+                                        out: *mut rh_enumerated) -> c_int;
     pub fn rh_sstore_set_host_tier(store: *mut rh_sstore, enable: c_int, round_max: u64) -> c_int;
     pub fn rh_sstore_set_tier_policy(store: *mut rh_sstore, keep_fresh: c_int) -> c_int;
     pub fn rh_sstore_reserve(store: *mut rh_sstore, rows: u64, batch_rows: u64) -> c_int;

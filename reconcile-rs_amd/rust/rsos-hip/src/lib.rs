@@ -367,6 +367,16 @@ impl<K: GpuKey, V: GpuRecord> HipFingerprintMap<K, V> {
         )
     }
 
+    /// The keys of a round's `enumeration_ranges` (the IDLISTs this side sends), one `Vec` per range,
+    /// in one call (`rh_store_enumerate_segments`): one device round trip, or none with a fresh host
+    /// tier, where `Rsos::enumerate` per range costs a rank and a key dump each.
+    pub fn enumerate_ranges(&self, enumeration_ranges: &[rbsr::EnumerationRange<K>]) -> Vec<Vec<K>> {
+        let _g = self.round_mu.lock().unwrap_or_else(|e| e.into_inner());
+        let store = self.store.0;
+        // SAFETY: the handle is live for &self; run_enumerate passes valid range buffers.
+        round::run_enumerate(|r, m, o| unsafe { ffi::rh_store_enumerate_segments(store, r, m, o) }, enumeration_ranges)
+    }
+
     /// `protocol_round` under `FixedFanOut(fan_out)` (16 = `protocol_round`'s default).
     pub fn protocol_round_fixed(
         &self,

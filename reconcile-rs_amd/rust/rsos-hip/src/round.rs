@@ -111,3 +111,57 @@ pub(crate) fn run_round<K: GpuKey>(
         dropped_malformed: oc.dropped_malformed as usize,
     }
 }
+
+/// The keys of a round's `enumeration_ranges`, one `Vec` per range, in one store call
+/// (`rh_store_enumerate_segments` / `rh_sstore_enumerate_segments`) where `Rsos::enumerate`
+/// (rsos/src/rsos_trait.rs:73-83) is asked range by range.  `call(ranges, max_rows, out)` is one of
+/// the two entry points on the caller's store; the answer points into the store's own buffer, read
+/// here before anything else can call the store (the caller holds its round lock).  An enumeration
+/// range's start is Included or Unbounded, its end Excluded or Unbounded (rbsr/src/protocol.rs).
+pub(crate) fn run_enumerate<K: GpuKey>(
+    call: impl FnOnce(*const ffi::rh_segments, u64, *mut ffi::rh_enumerated) -> c_int,
+    ranges: &[rbsr::EnumerationRange<K>],
+) -> Vec<Vec<K>> {
+    let kl = K::LEN as usize;
+    let n = ranges.len();
+    let mut sk = vec![0u8; n.max(1)];
+    let mut ek = vec![0u8; n.max(1)];
+    let mut skeys = vec![0u8; n * kl + 1];
+    let mut ekeys = vec![0u8; n * kl + 1];
+    for (j, (start, end)) in ranges.iter().enumerate() {
+        if let Bound::Included(k) | Bound::Excluded(k) = start {
+            sk[j] = 1;
+            skeys[j * kl..(j + 1) * kl].copy_from_slice(&k.column_bytes());
+        }
+        if let Bound::Included(k) | Bound::Excluded(k) = end {
+            ek[j] = 1;
+            ekeys[j * kl..(j + 1) * kl].copy_from_slice(&k.column_bytes());
+        }
+    }
+    let input = ffi::rh_segments {
+        start_kinds: sk.as_mut_ptr(),
+        start_keys: skeys.as_mut_ptr() as *mut c_void,
+        end_kinds: ek.as_mut_ptr(),
+        end_keys: ekeys.as_mut_ptr() as *mut c_void,
+        aggregates: std::ptr::null_mut(),
+        n,
+        cap: n,
+    };
+    let mut out = ffi::rh_enumerated {
+        first_ranks: std::ptr::null(),
+        offsets: std::ptr::null(),
+        keys: std::ptr::null(),
+        n: 0,
+        rows: 0,
+    };
+    check(call(&input, 0, &mut out), "enumerate_segments");
+    // SAFETY: the library filled out.offsets with n + 1 entries and out.keys with out.rows rows of
+    // kl bytes, valid until the store's next enumerate call, which the caller's round lock excludes.
+    unsafe {
+        let offs = std::slice::from_raw_parts(out.offsets, n + 1);
+        let rows = std::slice::from_raw_parts(out.keys as *const u8, out.rows as usize * kl);
+        (0..n)
+            .map(|j| (offs[j] as usize..offs[j + 1] as usize).map(|t| K::from_column_bytes(&rows[t * kl..(t + 1) * kl])).collect())
+            .collect()
+    }
+}

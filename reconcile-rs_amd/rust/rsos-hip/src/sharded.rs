@@ -21,7 +21,7 @@ use std::os::raw::{c_int, c_void};
 
 use rsos::{Aggregate, Fingerprint, Rsos};
 
-use crate::round::{run_round, RoundPolicy};
+use crate::round::{run_enumerate, run_round, RoundPolicy};
 use crate::{check, ffi, schema, sorted, Batch, GpuKey, GpuRecord, RoundCounts};
 
 /// The library's sharded store, owned (its one `Drop`; see `StoreHandle`).
@@ -226,6 +226,15 @@ impl<K: GpuKey, V: GpuRecord> HipShardedMap<K, V> {
             child_ranges,
             enumeration_ranges,
         )
+    }
+
+    /// The keys of a round's `enumeration_ranges`, one `Vec` per range, in one call
+    /// (`rh_sstore_enumerate_segments`): a range that straddles shards is its pieces in shard order.
+    pub fn enumerate_ranges(&self, enumeration_ranges: &[rbsr::EnumerationRange<K>]) -> Vec<Vec<K>> {
+        let _g = self.round_mu.lock().unwrap_or_else(|e| e.into_inner());
+        let store = self.store.0;
+        // SAFETY: the handle is live for &self; run_enumerate passes valid range buffers.
+        run_enumerate(|r, m, o| unsafe { ffi::rh_sstore_enumerate_segments(store, r, m, o) }, enumeration_ranges)
     }
 
     /// The device holds exactly the host index.
