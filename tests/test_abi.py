@@ -7,6 +7,8 @@ import re
 import numpy as np
 import pytest
 
+from records_common import M256
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "rsos_hip.h")
 
@@ -94,7 +96,7 @@ def test_host_fingerprint_group(rsos_hip_lib, golden):
         assert (back == a).all()
         ai = sum(int(x) << (64 * i) for i, x in enumerate(a))
         bi = sum(int(x) << (64 * i) for i, x in enumerate(b))
-        assert sum(int(x) << (64 * i) for i, x in enumerate(s)) == (ai + bi) % (1 << 256)
+        assert sum(int(x) << (64 * i) for i, x in enumerate(s)) == (ai + bi) % M256
 
 
 def test_python_value_types_mirror_reference(rsos_hip_lib):

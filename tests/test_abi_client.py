@@ -10,6 +10,7 @@ import pytest
 
 import oracle as O
 import rbsr as OR
+from recon_common import _ftm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLIENT = os.path.join(ROOT, "reconcile-rs_amd", "examples", "abi_client")
@@ -32,12 +33,6 @@ def _recs(keys, vals):
                      v.view(np.uint8).reshape(-1, 8))
 
 
-def _ftm(keys, vals):
-    t = O.FingerprintTreeMap(_recs(keys, vals))
-    t.fill(0, len(keys))
-    return t
-
-
 def _agg(d):
     return [int(x, 16) for x in d["fp"]], int(d["size"])
 
@@ -56,7 +51,7 @@ def test_c_client_against_oracle(gpu, oracle_lib):
     keys = sorted(set(next(g) for _ in range(n)))
     m = len(keys)
     vals = [next(g) for _ in range(m)]
-    t = _ftm(keys, vals)
+    t = _ftm(_recs(keys, vals))
     assert got["n"] == got["size"] == m
     assert _agg(got["root"]) == (list(t.root()[0]), m)
     probe = keys[m // 3] + 1
@@ -74,7 +69,7 @@ def test_c_client_against_oracle(gpu, oracle_lib):
     del content[keys[20]]
     assert (got["batch"]["new"], got["batch"]["overwritten"], got["batch"]["deleted"]) == (new, 1, 1)
     k2 = sorted(content)
-    t2 = _ftm(k2, [content[k] for k in k2])
+    t2 = _ftm(_recs(k2, [content[k] for k in k2]))
     assert _agg(got["root_after_batch"]) == (list(t2.root()[0]), len(k2))
     # the reconciliation: the literal driver over the two trees
     va, vb = OR.FtmView(t2, True), OR.FtmView(t, True)

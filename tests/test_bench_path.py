@@ -17,8 +17,9 @@ import sys
 
 import pytest
 
+from records_common import M256, row_int
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-M256 = 1 << 256
 
 
 def _bench(args, env_extra=None, timeout=240):
@@ -44,10 +45,6 @@ def test_bench_refuses_world_size_mismatch():
     r = _bench(["--gpus", "2", "--steps", "1"], env_extra={"WORLD_SIZE": "3", "RANK": "0"}, timeout=120)
     assert r.returncode != 0
     assert "WORLD_SIZE=3" in (r.stderr + r.stdout)
-
-
-def _agg_int(row):
-    return sum((int(x) & (2**64 - 1)) << (64 * i) for i, x in enumerate(row[:4]))
 
 
 @pytest.mark.gpu
@@ -77,7 +74,7 @@ def test_bench_world2_gloo_equals_single_process(tmp_path, gpu):
     limbs16 = fps.view(torch.int16).to(torch.int64) & 0xFFFF
     col = limbs16.sum(dim=0).cpu().tolist()
     want = sum(int(c) << (16 * i) for i, c in enumerate(col)) % M256
-    assert sum(_agg_int(r) for r in a["ranges"]) % M256 == want
+    assert sum(row_int(r) for r in a["ranges"]) % M256 == want
     assert sum(int(r[4]) for r in a["ranges"]) == total
     # equal-count ranges: range j holds rows [total*j/16, total*(j+1)/16)
     assert [int(r[4]) for r in a["ranges"]] == [total * (j + 1) // 16 - total * j // 16 for j in range(16)]

@@ -10,8 +10,7 @@ import numpy as np
 import pytest
 
 import pyref as P
-
-M256 = 1 << 256
+from records_common import fold
 
 
 def test_encoder_matches_oracle_restatement():
@@ -41,7 +40,7 @@ def _oracle_root(O, recs):
     if not recs:
         return 0
     fps = O.lift_encoded(recs, threads=8)
-    return sum(int.from_bytes(f.tobytes(), "little") for f in fps) % M256
+    return fold(fps)
 
 
 @pytest.mark.gpu
@@ -208,5 +207,5 @@ def test_fixed_length_records_take_fixed_kernel(gpu, oracle_lib):
                 hi = int(rng.integers(lo, len(keys) + 1))
                 a = m.aggregates_ranks([lo], [hi])[0]
                 assert a.size == hi - lo
-                assert a.fingerprint.to_int() == sum(int.from_bytes(f.tobytes(), "little") for f in fps[lo:hi]) % M256
+                assert a.fingerprint.to_int() == fold(fps[lo:hi])
         m.close()

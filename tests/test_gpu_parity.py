@@ -12,22 +12,9 @@ import types
 import numpy as np
 import pytest
 
+from records_common import M256, fp_int, limbs_int, oracle_records, row_int
+
 pytestmark = pytest.mark.gpu
-
-M256 = 1 << 256
-
-
-def fp_int(b) -> int:
-    return int.from_bytes(bytes(b), "little")
-
-
-def limbs_int(l) -> int:
-    return sum(int(x) << (64 * i) for i, x in enumerate(l))
-
-
-def agg_int(row) -> int:
-    """row of an (r, 5) int64 aggregate tensor -> fingerprint as int"""
-    return sum((int(x) & (2**64 - 1)) << (64 * i) for i, x in enumerate(row[:4]))
 
 
 def dev_cols(torch, schema_d, n, keys, values, phys=None, logical=None, node=None, tags=None):
@@ -128,11 +115,6 @@ SHAPES = [("u32", "u32"), ("u64", "u64"), ("u64", "bytes64"), ("bytes16", "bytes
           ("u64", "unit")]
 
 
-def oracle_records(O, schema, h):
-    sch = O.Schema(schema.key_kind, schema.key_len, schema.value_kind, schema.value_len, schema.record_kind, 0)
-    return O.Records(sch, h["keys"], h.get("values"), h.get("phys"), h.get("logical"), h.get("node"), h.get("tags"))
-
-
 @pytest.mark.parametrize("kind", ["plain", "dated", "projection"])
 @pytest.mark.parametrize("shape", SHAPES)
 def test_random_batches_bit_exact(gpu, oracle_lib, shape, kind):
@@ -201,7 +183,7 @@ def test_encoded_short_mix(gpu, oracle_lib):
     fps, bs = lift_encoded(data, torch.from_numpy(offs).cuda())
     want = oracle_lib.lift_encoded(blobs, threads=8)
     assert np.array_equal(fps.cpu().numpy(), want)
-    tot = sum(int.from_bytes(f.tobytes(), "little") for f in want[:256]) % (1 << 256)
+    tot = sum(int.from_bytes(f.tobytes(), "little") for f in want[:256]) % M256
     assert int.from_bytes(bs.cpu().numpy()[0].tobytes(), "little") == tot
 
 
@@ -246,7 +228,7 @@ def test_fixed_length_records(gpu, oracle_lib, length, offset):
     fps, bs = lift_fixed(dev[offset:offset + raw.size], length, n=n)
     want = oracle_lib.lift_encoded(blobs, threads=8)
     assert np.array_equal(fps.cpu().numpy(), want)
-    tot = sum(int.from_bytes(f.tobytes(), "little") for f in want[256:512]) % (1 << 256)
+    tot = sum(int.from_bytes(f.tobytes(), "little") for f in want[256:512]) % M256
     assert int.from_bytes(bs.cpu().numpy()[1].tobytes(), "little") == tot
 
 
@@ -353,7 +335,7 @@ def test_range_aggregates_match_prefix_sums(gpu, oracle_lib):
             h2 = min(int(h), n)
             l2 = min(int(l), h2)
             assert int(out[j][4]) == h2 - l2
-            assert agg_int(out[j]) == (pref[h2] - pref[l2]) % M256, (j, l, h)
+            assert row_int(out[j]) == (pref[h2] - pref[l2]) % M256, (j, l, h)
 
 
 def test_combine_aggregates(gpu):
@@ -366,8 +348,8 @@ def test_combine_aggregates(gpu):
     parts[1, 0, :4] = [1, 0, 0, 0]
     out = combine_aggregates(torch.from_numpy(parts).cuda()).cpu().numpy()
     for j in range(16):
-        want = sum(agg_int(parts[p, j]) for p in range(8)) % M256
-        assert agg_int(out[j]) == want
+        want = sum(row_int(parts[p, j]) for p in range(8)) % M256
+        assert row_int(out[j]) == want
         assert int(out[j][4]) == int(parts[:, j, 4].sum())
 
 
@@ -510,8 +492,8 @@ def test_full_size_config2_properties(gpu, oracle_lib):
     lo_t = torch.tensor([0, 0, 1234567], dtype=torch.int64, device="cuda")
     hi_t = torch.tensor([n, 1234567, n], dtype=torch.int64, device="cuda")
     out = range_aggregates(fps, bs, ss, lo_t, hi_t).cpu().numpy()
-    assert agg_int(out[0]) == want_root and int(out[0][4]) == n
-    assert (agg_int(out[1]) + agg_int(out[2])) % M256 == want_root
+    assert row_int(out[0]) == want_root and int(out[0][4]) == n
+    assert (row_int(out[1]) + row_int(out[2])) % M256 == want_root
 
 
 @pytest.mark.parametrize("value,n", [("bytes64", 100_000_000), ("bytes1024", 100_000_000)],
@@ -547,8 +529,8 @@ def test_full_size_100m_properties(gpu, oracle_lib, value, n):
     lo_t = torch.tensor([0] + cuts[:-1], dtype=torch.int64, device="cuda")
     hi_t = torch.tensor([n] + cuts[1:], dtype=torch.int64, device="cuda")
     out = range_aggregates(fps, bs, ss, lo_t, hi_t).cpu().numpy()
-    assert agg_int(out[0]) == want_root and int(out[0][4]) == n
-    assert sum(agg_int(r) for r in out[1:]) % M256 == want_root
+    assert row_int(out[0]) == want_root and int(out[0][4]) == n
+    assert sum(row_int(r) for r in out[1:]) % M256 == want_root
     assert [int(r[4]) for r in out[1:]] == [b - a for a, b in zip(cuts, cuts[1:])]
 
 

@@ -12,20 +12,13 @@ import os
 import numpy as np
 import pytest
 
+from records_common import M256, fp_int, limbs_int, oracle_records
+
 pytestmark = pytest.mark.gpu
 
-M256 = 1 << 256
 SWITCH = "RSOS_HIP_LIFT_PRIO"
 SIZES = [1, 63, 64, 65, 255, 256, 257, 511, 512, 513, 1023, 1025, 4099]
 NMAX = max(SIZES)
-
-
-def fp_int(b) -> int:
-    return int.from_bytes(bytes(b), "little")
-
-
-def limbs_int(l) -> int:
-    return sum(int(x) << (64 * i) for i, x in enumerate(l))
 
 
 class form:
@@ -43,11 +36,6 @@ class form:
             del os.environ[SWITCH]
         else:
             os.environ[SWITCH] = self.old
-
-
-def oracle_records(O, schema, h):
-    sch = O.Schema(schema.key_kind, schema.key_len, schema.value_kind, schema.value_len, schema.record_kind, 0)
-    return O.Records(sch, h.get("keys"), h.get("values"), h.get("phys"), h.get("logical"), h.get("node"), h.get("tags"))
 
 
 def head(cols, n):
@@ -149,14 +137,14 @@ def test_scattered_lift_through_a_store(gpu, oracle_lib):
     from rsos_hip.synth import make_records, to_host
     s = RecordSchema.dated("bytes16", "bytes64")
 
-    def fold(cols):
+    def lifted_sum(cols):
         return sum(fp_int(f) for f in oracle_records(oracle_lib, s, to_host(cols)).lift(threads=8))
 
     base = make_records(s, 5000, seed=42, key_space=5000)
     batches = [make_records(s, m, seed=70 + m, random_keys=True) for m in (1000, 70_000)]
-    wants, acc, size = [], fold(base), 5000
+    wants, acc, size = [], lifted_sum(base), 5000
     for b in batches:
-        acc += fold(b)
+        acc += lifted_sum(b)
         size += b["keys"].shape[0]
         wants.append((acc % M256, size))
     for prio in (True, False):

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import pyref as P
+from records_common import M256
 
 
 def limbs(b: bytes):
@@ -53,7 +54,7 @@ def test_golden_entry_fingerprint(golden, oracle_lib):
 def test_carry_borrow_kats(golden):
     for kat in golden["reference"]["carry_borrow"]:
         a, b, out = to_int(kat["a"]), to_int(kat["b"]), to_int(kat["out"])
-        got = (a + b) % (1 << 256) if kat["op"] == "add" else (a - b) % (1 << 256)
+        got = (a + b) % M256 if kat["op"] == "add" else (a - b) % M256
         assert got == out
 
 
@@ -162,12 +163,12 @@ def test_ftm_big_test_invariants(oracle_lib):
     last = {}
     for i, k in enumerate(keys.tolist()):
         last[k] = i
-    s = sum(int.from_bytes(fps[i].tobytes(), "little") for i in last.values()) % (1 << 256)
+    s = sum(int.from_bytes(fps[i].tobytes(), "little") for i in last.values()) % M256
     assert sum(x << (64 * j) for j, x in enumerate(root[0])) == s
     # partition additivity agg(..mid) + agg(mid..) == agg(..)
     mid = np.uint64(2**62).tobytes()
     a, b = t.aggregate(None, mid), t.aggregate(mid, None)
-    tot = (sum(x << (64 * j) for j, x in enumerate(a[0])) + sum(x << (64 * j) for j, x in enumerate(b[0]))) % (1 << 256)
+    tot = (sum(x << (64 * j) for j, x in enumerate(a[0])) + sum(x << (64 * j) for j, x in enumerate(b[0]))) % M256
     assert tot == s and a[1] + b[1] == root[1]
 
 
@@ -182,7 +183,7 @@ def test_ftm_overwrite_is_a_delta(oracle_lib):
     last = {}
     for i, k in enumerate(keys.tolist()):
         last[k] = i
-    s = sum(int.from_bytes(fps[i].tobytes(), "little") for i in last.values()) % (1 << 256)
+    s = sum(int.from_bytes(fps[i].tobytes(), "little") for i in last.values()) % M256
     root = t.root()
     assert root[1] == len(last)
     assert sum(x << (64 * j) for j, x in enumerate(root[0])) == s
@@ -207,7 +208,7 @@ def test_ftm_aggregate_brute_force_every_boundary_pair(oracle_lib):
             fp, size = t.aggregate(lob, hib)
             sel = [i for i in range(n) if max(lo, 0) <= keys[i] < max(hi, 0)]
             assert size == len(sel)
-            assert sum(x << (64 * j) for j, x in enumerate(fp)) == sum(fps[i] for i in sel) % (1 << 256)
+            assert sum(x << (64 * j) for j, x in enumerate(fp)) == sum(fps[i] for i in sel) % M256
             assert t.rank(lob) == sum(1 for k in keys if k < max(lo, 0))
 
 

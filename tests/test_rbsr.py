@@ -11,50 +11,10 @@ import pytest
 
 import oracle as O
 import rbsr as OR  # oracle/rbsr.py
-
-
-@pytest.fixture(autouse=True, params=["device", "host_tier"])
-def store_tier(request):
-    """Every GPU store of this module answers from the device, then from the host tier
-    (rh_store_set_host_tier): the answers must be identical."""
-    import rsos_hip.store as S
-    old = S.DEFAULT_HOST_TIER
-    S.DEFAULT_HOST_TIER = request.param == "host_tier"
-    yield request.param
-    S.DEFAULT_HOST_TIER = old
+from recon_common import _ftm, _norm, _outcome, _u32_recs, reconcile, store_tier  # noqa: F401 (store_tier: autouse here)
 
 
 # ---- helpers ---------------------------------------------------------------------------------
-
-def _u32_recs(pairs):
-    pairs = sorted(pairs)
-    k = np.array([a for a, _ in pairs], np.uint32)
-    v = np.array([b for _, b in pairs], np.uint32)
-    n = len(pairs)
-    return O.Records(O.Schema(O.KEY_U32, 4, O.VAL_U32, 4, O.REC_PLAIN, 0), k.view(np.uint8).reshape(n, 4),
-                     v.view(np.uint8).reshape(n, 4))
-
-
-def _ftm(recs):
-    t = O.FingerprintTreeMap(recs)
-    t.fill(0, recs.n)
-    return t
-
-
-def _agg_t(a):
-    """rsos_hip Aggregate -> the oracle's (fp limbs, size)."""
-    return tuple(int(x) for x in a.fingerprint.limbs), int(a.size)
-
-
-def _norm(children):
-    out = []
-    for c in children:
-        if isinstance(c, tuple):
-            out.append(c)
-        else:
-            out.append((c.start, c.end, _agg_t(c.aggregate)))
-    return out
-
 
 class BatchedFtm:
     """The two batched questions of rsos_hip.rbsr answered by the oracle FTM (host-logic check)."""
@@ -97,23 +57,6 @@ def _to_product(segs):
     from rsos_hip import Aggregate, Fingerprint
     from rsos_hip.wire import RangeAggregate
     return [RangeAggregate(s, e, Aggregate(a[1], Fingerprint(tuple(a[0])))) for s, e, a in segs]
-
-
-def reconcile(a, b, round_fn, init, max_rounds=200):
-    """Ping-pong rounds starting from a's root at b; per round: (children, enumerations, outcome)."""
-    active = init(a)
-    sides = [b, a]
-    log, enums = [], {id(a): [], id(b): []}
-    for k in range(max_rounds):
-        if not active:
-            return log, enums[id(a)], enums[id(b)]
-        side = sides[k % 2]
-        children, en = [], []
-        outcome = round_fn(side, active, children, en)
-        log.append((_norm(children), list(en), outcome))
-        enums[id(side)].extend(en)
-        active = children
-    raise AssertionError("reconciliation did not terminate")
 
 
 def _covered(k, ranges, lt):
@@ -452,10 +395,6 @@ def test_gpu_soa_reconciliation_and_wire(gpu, oracle_lib):
     assert k == len(want)
     ga.close()
     gb.close()
-
-
-def _outcome(o):
-    return (o.skipped, o.enumerated, o.split, o.children, o.dropped_malformed)
 
 
 @pytest.mark.gpu

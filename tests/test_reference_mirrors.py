@@ -16,32 +16,8 @@ import pytest
 
 import oracle as O
 import rbsr as OR  # oracle/rbsr.py
-
-
-@pytest.fixture(autouse=True, params=["device", "host_tier"])
-def store_tier(request):
-    """Every GPU store of this module answers from the device, then from the host tier
-    (rh_store_set_host_tier): the answers must be identical."""
-    import rsos_hip.store as S
-    old = S.DEFAULT_HOST_TIER
-    S.DEFAULT_HOST_TIER = request.param == "host_tier"
-    yield request.param
-    S.DEFAULT_HOST_TIER = old
-
-
-def _u32_recs(pairs):
-    pairs = sorted(pairs)
-    k = np.array([a for a, _ in pairs], np.uint32)
-    v = np.array([b for _, b in pairs], np.uint32)
-    n = len(pairs)
-    return O.Records(O.Schema(O.KEY_U32, 4, O.VAL_U32, 4, O.REC_PLAIN, 0), k.view(np.uint8).reshape(n, 4),
-                     v.view(np.uint8).reshape(n, 4))
-
-
-def _ftm(recs):
-    t = O.FingerprintTreeMap(recs)
-    t.fill(0, recs.n)
-    return t
+from recon_common import _ftm, _u32_recs, store_tier  # noqa: F401 (store_tier: autouse here)
+from records_common import M256
 
 
 def oracle_diff(a, b):
@@ -127,7 +103,7 @@ def test_aggregate_every_boundary_pair(gpu, oracle_lib):
     for (lo, hi), a, rl, rh in zip(pairs, aggs, raw_lo, raw_hi):
         assert (int(rl), int(rh)) == (lo, hi)
         assert a.size == hi - lo
-        assert a.fingerprint.to_int() == (fold[hi] - fold[lo]) % (1 << 256), (lo, hi)
+        assert a.fingerprint.to_int() == (fold[hi] - fold[lo]) % M256, (lo, hi)
     st.close()
 
 

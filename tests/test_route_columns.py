@@ -14,6 +14,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from records_common import _key_ints, _splitters
+
 NS = [0, 1, 15, 16, 17, 255, 256, 257, 4097, 70001]
 GS = [1, 2, 4, 7, 64]
 GUARD = 0xA5
@@ -37,17 +39,6 @@ def _schema(kind, key, value):
     return getattr(RecordSchema, kind)(key, value)
 
 
-def _key_ints(sch, rows):
-    """each key row as a Python int whose order is the key order"""
-    rows = np.ascontiguousarray(rows).reshape(-1, sch.key_row)
-    if sch.key_kind in (1, 2):
-        return rows.view("<u4" if sch.key_row == 4 else "<u8").ravel().astype(object)
-    out = np.empty(len(rows), object)
-    for i, r in enumerate(rows):
-        out[i] = int.from_bytes(r.tobytes(), "big")
-    return out
-
-
 def _gen(rng, sch, n, tags, ops, few_keys=0):
     kl, vl = sch.key_row, sch.value_row
     keys = rng.integers(0, 256, size=(n, kl), dtype=np.uint8)
@@ -63,19 +54,6 @@ def _gen(rng, sch, n, tags, ops, few_keys=0):
     if tags:
         cols["tags"] = (rng.random(n) < 0.3).astype(np.uint8)
     return cols, ((rng.random(n) < 0.4).astype(np.uint8) if ops else None)
-
-
-def _splitters(rng, sch, shards, cols):
-    """shards - 1 non-decreasing key rows: some drawn from the batch's own keys (a key equal to a
-    splitter belongs to the shard above it), the rest random"""
-    kl = sch.key_row
-    sp = rng.integers(0, 256, size=(shards - 1, kl), dtype=np.uint8)
-    n = len(cols["keys"])
-    for j in range(0, shards - 1, 2):
-        if n:
-            sp[j] = cols["keys"][rng.integers(0, n)]
-    order = np.argsort(_key_ints(sch, sp), kind="stable") if shards > 1 else np.zeros(0, np.int64)
-    return np.ascontiguousarray(sp[order])
 
 
 def _route_and_check(gpu, sch, sp, shards, cols, ops):

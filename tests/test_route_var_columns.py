@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_route_columns import _key_ints, _splitters
+from records_common import _key_ints, _splitters
 
 NS = [1, 15, 17, 2047, 2049, 5000]
 GS = [1, 2, 7, 64]

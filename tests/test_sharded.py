@@ -15,30 +15,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_small_batch import M256, Model, _batch, _gen
+from records_common import M256, ColumnModel, _batch, _drive, _gen, _order, _sorted_unique, agg_int
 
 G = 4
 
 
-def _sorted_unique(sch, cols):
-    k = cols["keys"]
-    if sch.key_kind in (1, 2):
-        order = np.argsort(k.copy().view("<u4" if sch.key_row == 4 else "<u8").ravel(), kind="stable")
-    else:
-        order = np.lexsort(k.T[::-1])
-    cols = {c: v[order] for c, v in cols.items()}
-    _, first = np.unique(cols["keys"], axis=0, return_index=True)
-    keep = np.sort(first)
-    return {c: v[keep] for c, v in cols.items()}
-
-
-def _fp_int(agg):
-    return sum(int(x) << (64 * i) for i, x in enumerate(agg.fingerprint.limbs))
-
-
 def _want_range(model, sch, lo, lk, hi, hk):
     """the oracle fold over keys in the range (bound kinds 'included' / 'excluded' / 'unbounded')"""
-    from test_small_batch import _order
     tot, n = 0, 0
     for k, f in model.d.items():
         o = _order(sch, k)
@@ -51,19 +34,6 @@ def _want_range(model, sch, lo, lk, hi, hk):
     return tot % M256, n
 
 
-def _drive(a, b, policy):
-    """a whole reconciliation between two maps, native rounds: every round's output"""
-    from rsos_hip import rbsr as R
-    out, active, sides, k = [], R.initial_ranges(a), [b, a], 0
-    while active and k < 64:
-        ch, en = [], []
-        o = R.protocol_round_with_policy(sides[k % 2], policy, active, ch, en)
-        out.append(([(c.start, c.end, c.aggregate) for c in ch], en,
-                    (o.skipped, o.enumerated, o.split, o.children, o.dropped_malformed)))
-        active, k = ch, k + 1
-    return out
-
-
 def _check_same(sh, one, model, sch, rng):
     from rsos_hip.store import KeyRange
     n = one.size()
@@ -71,12 +41,11 @@ def _check_same(sh, one, model, sch, rng):
     assert sum(sh.sizes()) == n
     root = sh.aggregate()
     assert root == one.aggregate()
-    assert (_fp_int(root), root.size) == model.root()
+    assert (agg_int(root), root.size) == model.root()
     keys = model.sorted_keys()
     key_out = one._key_out
     # every shard holds exactly its splitter range
     spl = sh.splitters
-    from test_small_batch import _order
     ok = lambda k: _order(sch, one._key_bytes(k))  # noqa: E731
     r0 = 0
     for s, size in enumerate(sh.sizes()):
@@ -117,7 +86,7 @@ def _check_same(sh, one, model, sch, rng):
             assert got == one.aggregate(rng_)
             want = _want_range(model, sch, ok(a) if rng_.start is not None else None, rng_.start_kind,
                                ok(b) if rng_.end is not None else None, rng_.end_kind)
-            assert (_fp_int(got), got.size) == want
+            assert (agg_int(got), got.size) == want
     # rank-range aggregates: across boundaries, inverted, past the end
     lo = [int(x) for x in rng.integers(0, n + 5, 50)] + [int(o) - 3 for o in offs[1:-1]] + [n - 1, 5]
     hi = [int(x) for x in rng.integers(0, n + 5, 50)] + [int(o) + 3 for o in offs[1:-1]] + [n + 10, 2]
@@ -150,7 +119,7 @@ def test_sharded_equals_single_store_and_oracle(gpu, oracle_lib, spec, tier, sha
     kind, kk, vk, tomb = spec
     sch = getattr(RecordSchema, kind)(kk, vk)
     rng = np.random.default_rng(11)
-    model = Model(oracle_lib, sch)
+    model = ColumnModel(oracle_lib, sch)
     cols = _sorted_unique(sch, _gen(rng, sch, 30000, tomb))
     one = GpuFingerprintStore(sch, host_tier=tier)
     sh = ShardedStore(sch, [0] * shards, host_tier=tier)
@@ -216,13 +185,13 @@ def test_sharded_edge_cases(gpu, oracle_lib):
     with pytest.raises(IndexError):
         sh.select(0)
     # single inserts into the empty map spread over every shard by the even cut
-    model = Model(oracle_lib, sch)
+    model = ColumnModel(oracle_lib, sch)
     b = _gen(rng, sch, 400, False)
     for i in range(400):
         sh.stage({c: v[i:i + 1] for c, v in b.items()}, np.zeros(1, np.uint8))
     model.apply(b, np.zeros(400, np.uint8))
     assert sh.size() == 400 and all(s > 50 for s in sh.sizes())
-    assert (_fp_int(sh.aggregate()), sh.size()) == model.root()
+    assert (agg_int(sh.aggregate()), sh.size()) == model.root()
     # splitters are only settable while empty
     with pytest.raises(A.RsosHipError):
         sh.set_splitters([1, 2, 3])

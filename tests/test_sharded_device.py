@@ -14,70 +14,15 @@ import os
 import numpy as np
 import pytest
 
-from test_sharded import _drive, _sorted_unique
-from test_small_batch import Model, _batch, _gen
+from ragged_snapshot_common import gen_records, ordered, schemas, to_dev, write_snapshot
+from records_common import ColumnModel, _batch, _devices, _dump, _gen, _key_rows, _same, _sorted_unique
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _devices(shards):
-    import torch
-    return [s % torch.cuda.device_count() for s in range(shards)]
 
 
 def _dev(cols, gpu):
     import torch
     return {c: torch.from_numpy(np.ascontiguousarray(v)).to(gpu) for c, v in cols.items()}
-
-
-def _key_rows(st):
-    from rsos_hip import _abi as A
-    n, kl = st.size(), st.schema.key_row
-    out = np.zeros((max(n, 1), kl), np.uint8)
-    A.check(st._f("keys")(st._h, 0, n, out.ctypes.data if n else None), "keys")
-    return out[:n]
-
-
-def _state(st, probes, ranges, selects):
-    """everything the issue lists, in a form that compares with =="""
-    from rsos_hip.store import KeyRange
-    n = st.size()
-    return {
-        "len": n,
-        "root": st.aggregate(),
-        "ranges": [st.aggregate(KeyRange(st._key_out(a.tobytes()), st._key_out(b.tobytes()))) for a, b in ranges],
-        "ranks": st.ranks(probes).tolist(),
-        "selects": [st.select(r) for r in selects if r < n],
-        "keys": _key_rows(st).tobytes(),
-        "fps": st.fingerprints().tobytes(),
-    }
-
-
-def _same(maps, rng, peer=None):
-    """all of `maps` (the device-fed map first) hold the same state"""
-    from rsos_hip import rbsr as R
-    rows = _key_rows(maps[0])
-    n, kl = rows.shape[0], maps[0].schema.key_row
-    pick = rows[rng.integers(0, n, 150)] if n else np.zeros((0, kl), np.uint8)
-    near = pick[:50].copy()
-    if len(near):
-        near[:, kl // 2] ^= 1  # keys that are mostly absent, next to present ones
-    probes = np.ascontiguousarray(np.concatenate([pick, near]))
-    order = np.lexsort(probes.T[::-1]) if maps[0].schema.key_kind not in (1, 2) else \
-        np.argsort(probes.copy().view("<u4" if kl == 4 else "<u8").ravel())
-    srt = probes[order]
-    ranges = [(srt[i], srt[-1 - i]) for i in range(min(16, len(srt) // 2))]
-    selects = sorted(set(int(x) for x in rng.integers(0, max(n, 1), 40)) | {0, max(n - 1, 0)})
-    want = _state(maps[0], probes, ranges, selects)
-    assert want["len"] == n
-    for other in maps[1:]:
-        got = _state(other, probes, ranges, selects)
-        for k in want:
-            assert got[k] == want[k], k
-    if peer is not None:
-        rounds = _drive(maps[0], peer, R.FixedFanOut(16))
-        for other in maps[1:]:
-            assert _drive(other, peer, R.FixedFanOut(16)) == rounds
 
 
 SPECS = [("dated", "bytes16", "bytes64", True), ("plain", "u64", "u64", False)]
@@ -98,7 +43,7 @@ def test_device_route_equals_host_route_and_one_store(gpu, oracle_lib, spec, sha
     maps = [dmap, one, hmap]
     for st in maps:
         st.set_compaction(6, 1024)
-    model = Model(oracle_lib, sch)
+    model = ColumnModel(oracle_lib, sch)
     even = dmap.splitters
 
     def batch(m, stage_first=0):
@@ -126,7 +71,7 @@ def test_device_route_equals_host_route_and_one_store(gpu, oracle_lib, spec, sha
     cols = _sorted_unique(sch, _gen(rng, sch, n + 40, tomb))
     cols = {c: v[:n] for c, v in cols.items()}
     assert len(cols["keys"]) == n
-    model = Model(oracle_lib, sch)
+    model = ColumnModel(oracle_lib, sch)
     model.apply(cols, np.zeros(n, np.uint8))
     dmap.load_bulk_device(_dev(cols, gpu))
     one.load_bulk_device(_dev(cols, gpu))
@@ -294,14 +239,9 @@ SNAP = [("b16_b64", False), ("str31_u64", True)]
 def _snap_maps(shape, shards=4):
     from rsos_hip import GpuFingerprintStore
     from rsos_hip.sharded import ShardedStore
-    from test_ragged_snapshot import schemas
     sd, sp, form = schemas(shape)
     return (ShardedStore(sd, _devices(shards)), ShardedStore(sp, _devices(shards)), GpuFingerprintStore(sd),
             GpuFingerprintStore(sp), form)
-
-
-def _dump(st):
-    return st.size(), st.aggregate(), _key_rows(st).tobytes(), st.fingerprints().tobytes()
 
 
 @pytest.mark.gpu
@@ -310,7 +250,6 @@ def test_sharded_snapshot_reload_equals_one_store(gpu, shape, ragged):
     from rsos_hip import _abi as A
     from rsos_hip.sharded import ShardedStore
     from rsos_hip.snapshot import load_snapshot
-    from test_ragged_snapshot import gen_records, ordered, to_dev, write_snapshot
     recs = ordered(shape, gen_records(shape, 3001, 0.2, unique=True), "sorted")
     data, end, starts = write_snapshot(shape, recs)
     sd, sp, od, op, form = _snap_maps(shape)

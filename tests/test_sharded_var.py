@@ -13,7 +13,8 @@ round against a peer."""
 import numpy as np
 import pytest
 
-from test_sharded_device import _devices, _dump, _key_rows, _same
+from ragged_snapshot_common import gen_records, ordered, schemas, to_dev, write_snapshot
+from records_common import _devices, _dump, _same
 
 SPECS = [("dated", "str31", True), ("plain", "u64", False)]
 
@@ -167,7 +168,6 @@ def test_var_sharded_snapshot_reload_equals_one_store(gpu):
     from rsos_hip import GpuFingerprintStore, _abi as A
     from rsos_hip.sharded import ShardedStore
     from rsos_hip.snapshot import load_snapshot
-    from test_ragged_snapshot import gen_records, ordered, schemas, to_dev, write_snapshot
     shape = "str31_var"
     recs = ordered(shape, gen_records(shape, 3001, 0.2, unique=True), "sorted")
     data, end, starts = write_snapshot(shape, recs)

@@ -14,91 +14,10 @@ lifts (oracle/oracle.c)."""
 import numpy as np
 import pytest
 
-M256 = 1 << 256
+from records_common import ColumnModel, _batch, _gen, _order
 
 SCHEMAS = [("dated", "bytes16", "bytes64", True), ("plain", "u64", "u64", False),
            ("projection", "bytes32", "bytes64", True), ("dated", "u32", "u32", True)]
-
-
-def _gen(rng, sch, n, tombstones):
-    """n random host rows of schema sch (keys distinct)."""
-    kl, vl = sch.key_row, sch.value_row
-    keys = rng.integers(0, 256, size=(n, kl), dtype=np.uint8)
-    cols = {"keys": keys, "values": rng.integers(0, 256, size=(n, vl), dtype=np.uint8)}
-    if sch.dated_kind:
-        cols["phys"] = rng.integers(0, 1 << 62, size=n, dtype=np.uint64)
-        cols["logical"] = rng.integers(0, 1 << 31, size=n, dtype=np.uint32)
-        cols["node"] = rng.integers(0, 1 << 62, size=n, dtype=np.uint64)
-    if tombstones:
-        cols["tags"] = (rng.random(n) < 0.1).astype(np.uint8)
-    return cols
-
-
-def _order(sch, k: bytes):
-    return int.from_bytes(k, "little") if sch.key_kind in (1, 2) else k
-
-
-class Model:
-    """FingerprintTreeMap's contents: key -> fingerprint (last write wins, deletes remove)."""
-
-    def __init__(self, O, sch):
-        self.O, self.sch, self.d = O, sch, {}
-        self.osch = O.Schema(sch.key_kind, sch.key_len, sch.value_kind, sch.value_len, sch.record_kind, 0)
-
-    def lifts(self, cols):
-        g = lambda c: cols.get(c)  # noqa: E731
-        return self.O.Records(self.osch, g("keys"), g("values"), g("phys"), g("logical"), g("node"), g("tags")).lift()
-
-    def apply(self, cols, ops):
-        """rows in order; returns (new, overwritten, deleted) as the store counts them for a batch
-        of distinct keys"""
-        fps = self.lifts(cols)
-        new = over = dele = 0
-        for i in range(len(ops)):
-            k = cols["keys"][i].tobytes()
-            live = k in self.d
-            if ops[i]:
-                dele += live
-                self.d.pop(k, None)
-            else:
-                new += not live
-                over += live
-                self.d[k] = fps[i].tobytes()
-        return new, over, dele
-
-    def root(self):
-        return sum(int.from_bytes(f, "little") for f in self.d.values()) % M256, len(self.d)
-
-    def sorted_keys(self):
-        return sorted(self.d, key=lambda k: _order(self.sch, k))
-
-
-def _batch(rng, sch, model, m, tombstones, repeats=False):
-    """m rows: fresh keys, overwrites of live keys, deletes of live and of absent keys; with
-    repeats, some keys appear two or three times (staged rows only)."""
-    cols = _gen(rng, sch, m, tombstones)
-    ops = np.zeros(m, np.uint8)
-    live = model.sorted_keys()
-    if live:
-        for i in range(m):
-            u = rng.random()
-            if u < 0.2:  # overwrite a live key
-                cols["keys"][i] = np.frombuffer(live[rng.integers(len(live))], np.uint8)
-            elif u < 0.27:  # delete a live key
-                cols["keys"][i] = np.frombuffer(live[rng.integers(len(live))], np.uint8)
-                ops[i] = 1
-            elif u < 0.3:  # delete an absent key
-                ops[i] = 1
-    if repeats and m > 2:
-        for i in range(1, m, 3):
-            cols["keys"][i] = cols["keys"][i - 1]
-            ops[i] = rng.integers(0, 2)
-    if not repeats:  # distinct keys: keep the first of any accidental repeat
-        _, first = np.unique(cols["keys"], axis=0, return_index=True)
-        keep = np.sort(first)
-        cols = {c: v[keep] for c, v in cols.items()}
-        ops = ops[keep]
-    return cols, ops
 
 
 def _run(O, spec, small_on, monkeypatch, seed=3):
@@ -111,7 +30,7 @@ def _run(O, spec, small_on, monkeypatch, seed=3):
     kind, kname, vname, tomb = spec
     sch = getattr(RecordSchema, kind)(kname, vname)
     rng = np.random.default_rng(seed)
-    model = Model(O, sch)
+    model = ColumnModel(O, sch)
     base = _gen(rng, sch, 6000, tomb)
     _, first = np.unique(base["keys"], axis=0, return_index=True)
     base = {c: v[np.sort(first)] for c, v in base.items()}
@@ -184,7 +103,7 @@ def test_staged_large_batch_keeps_last_operation(gpu, oracle_lib, monkeypatch):
     monkeypatch.delenv("RSOS_HIP_SMALL_MAX", raising=False)
     sch = RecordSchema.dated("bytes16", "bytes64")
     rng = np.random.default_rng(11)
-    model = Model(oracle_lib, sch)
+    model = ColumnModel(oracle_lib, sch)
     st = GpuFingerprintStore(sch)
     for rnd in range(3):
         cols, ops = _batch(rng, sch, model, 5000, True, repeats=True)

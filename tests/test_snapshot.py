@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import snapshot as OS  # oracle/snapshot.py
+from records_common import M256
 
 SHAPES = {  # name -> (key, value, oracle key kind, key form)
     "b16_b64": ("bytes16", "bytes64", "array", "array"),
@@ -249,7 +250,7 @@ def test_reload_full_size_properties(gpu):
     fps, _ = lift_records(sd, src, block_sums=False)
     limbs = fps.view(torch.int64).view(n, 4).cpu().numpy().view(np.uint64)
     total = sum(int(x) << (64 * i) for i, x in enumerate([int(limbs[:, j].astype(object).sum()) for j in range(4)]))
-    total %= 1 << 256
+    total %= M256
     agg = dated.aggregate()
     assert agg.size == n and agg.fingerprint.to_int() == total
 
@@ -326,7 +327,7 @@ def test_reload_into_one_store(gpu, oracle_lib, shape, which):
     probe = np.linspace(0, n - 1, 97).astype(np.int64)
     assert np.array_equal(st.ranks(np.ascontiguousarray(cols["keys"][probe])), probe)
     limbs = want.view(np.uint64).reshape(n, 4)
-    total = sum(int(limbs[:, j].astype(object).sum()) << (64 * j) for j in range(4)) % (1 << 256)
+    total = sum(int(limbs[:, j].astype(object).sum()) << (64 * j) for j in range(4)) % M256
     assert st.aggregate().fingerprint.to_int() == total
 
 

@@ -2,7 +2,7 @@
 RCNL v1 header and entries, the inverse of the ragged decode; rsos_hip.snapshot adds the tail's
 encoder and the file write.
 
-Expected bytes come from the pure-Python writer of tests/test_ragged_snapshot.py (write_snapshot,
+Expected bytes come from the pure-Python writer of tests/ragged_snapshot_common.py (write_snapshot,
 tail_bytes), read back by its sequential parser where a case has no writer-side expectation.
 """
 import ctypes as C
@@ -15,8 +15,9 @@ import struct
 import numpy as np
 import pytest
 
-from test_ragged_snapshot import (DECODE_SHAPES, MEMBERS, SHAPES, gen_records, key_rows, key_width, ordered,
-                                  parse_snapshot, schemas, tail_bytes, val_width, write_snapshot)
+from ragged_snapshot_common import (DECODE_SHAPES, MEMBERS, SHAPES, gen_records, key_rows, ordered, parse_snapshot, schemas,
+                                    tail_bytes, write_snapshot)
+from records_common import key_width, val_width
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = [(0, 0.0), (1, 0.0), (1, 1.0), (63, 0.25), (64, 0.25), (65, 0.25), (777, 0.25), (20000, 0.1), (5000, 1.0)]
@@ -46,7 +47,7 @@ def host_columns(shape, recs):
     return cols
 
 
-def to_device(cols):
+def to_cuda(cols):
     import torch
 
     def up(a):
@@ -175,7 +176,7 @@ def test_encode_is_bit_exact(gpu, shape, n, tomb):
     from rsos_hip.snapshot import encode_entries_device
     recs, want = expected(shape, n, tomb)
     sd, _, form = schemas(shape)
-    got, info = encode_entries_device(sd, to_device(host_columns(shape, recs)), form)
+    got, info = encode_entries_device(sd, to_cuda(host_columns(shape, recs)), form)
     assert (info.entries, info.tombstones, info.entries_end, info.keys) == (n, sum(r[2] for r in recs), len(want), n)
     assert got.numel() == len(want)
     assert got.cpu().numpy().tobytes() == want
@@ -196,7 +197,7 @@ def test_long_values(gpu, shape):
         recs.append((r[0], r[1], 1, b"") if ln is None else (r[0], r[1], 0, rng.bytes(ln)))
     data, end, _ = write_snapshot(shape, recs)
     sd, _, form = schemas(shape)
-    got, info = encode_entries_device(sd, to_device(host_columns(shape, recs)), form)
+    got, info = encode_entries_device(sd, to_cuda(host_columns(shape, recs)), form)
     assert (info.entries, info.tombstones, info.entries_end) == (40, sum(r[2] for r in recs), end)
     assert got.cpu().numpy().tobytes() == data[:end]
 
@@ -207,7 +208,7 @@ def test_bounds(gpu, shape):
     from rsos_hip import _abi as A
     recs, want = expected(shape, 777, 0.25)
     end = len(want)
-    cols = to_device(host_columns(shape, recs))
+    cols = to_cuda(host_columns(shape, recs))
     tomb = sum(r[2] for r in recs)
     # cap = end: exact, and nothing behind it
     out = guarded(end)
@@ -236,7 +237,7 @@ def test_no_tags_means_all_present(gpu, shape):
     from rsos_hip.snapshot import encode_entries_device
     recs = gen_records(shape, 300, 0.0)
     sd, _, form = schemas(shape)
-    cols = to_device(host_columns(shape, recs))
+    cols = to_cuda(host_columns(shape, recs))
     assert int(cols["tags"].sum()) == 0
     with_tags, _ = encode_entries_device(sd, cols, form)
     without, info = encode_entries_device(sd, dict(cols, tags=None), form)
@@ -251,7 +252,7 @@ def test_round_trip_through_the_decoder(gpu, shape):
     from rsos_hip.snapshot import decode_entries_device, encode_entries_device
     recs = gen_records(shape, 777, 0.25)
     sd, _, form = schemas(shape)
-    cols = to_device(host_columns(shape, recs))
+    cols = to_cuda(host_columns(shape, recs))
     data, info = encode_entries_device(sd, cols, form)
     back, info2 = decode_entries_device(sd, data.clone(), form, ragged=True)
     assert (info2.entries, info2.tombstones, info2.entries_end) == (777, info.tombstones, info.entries_end)
@@ -279,7 +280,7 @@ def test_round_trip_through_the_reload(gpu, shape):
     from rsos_hip.snapshot import encode_entries_device, load_snapshot
     recs = ordered(shape, gen_records(shape, 3000, 0.2, unique=True), "sorted")
     sd, sp, form = schemas(shape)
-    cols = to_device(host_columns(shape, recs))
+    cols = to_cuda(host_columns(shape, recs))
     data, info = encode_entries_device(sd, cols, form)
     load_cols = dict(cols)
     if isinstance(cols["values"], tuple):
@@ -326,7 +327,7 @@ def test_malformed_columns_stay_in_bounds(gpu, what):
         tags = host["tags"].copy()
         tags[::5] = 7
         host["tags"] = tags
-    cols = to_device(host)
+    cols = to_cuda(host)
     rc, info = encode_raw(shape, cols, None, 0)
     assert rc == A.OK
     end = int(info.entries_end)
@@ -357,7 +358,7 @@ def test_save_snapshot_writes_a_file_the_reload_reads(gpu, tmp_path):
     sd, sp, form = schemas(shape)
     acks = {pack_str_keys([recs[3][0]], 32)[0].tobytes(): PEERS}
     path = tmp_path / "state.rcnl"
-    info = save_snapshot(path, sd, to_device(host_columns(shape, recs)), MEMBERS, acks, form)
+    info = save_snapshot(path, sd, to_cuda(host_columns(shape, recs)), MEMBERS, acks, form)
     data = path.read_bytes()
     assert data == write_snapshot(shape, recs, MEMBERS, {recs[3][0]: PEERS})[0]
     assert sorted(os.listdir(tmp_path)) == ["state.rcnl"]

@@ -4,8 +4,9 @@ names, examples/k8s/main.rs:53 -- stays in the column store.  At this width the 
 behind it and the first value words can straddle the edge between message blocks 0 and 1, and a
 tombstone's message can take two blocks.
 
-Expected fingerprints come from the oracle alone, as in test_str_keys.py: canonical bytes built
-with oracle/pyref.py's typed model and hashed by the C oracle (oracle.lift_encoded).
+Expected fingerprints come from the oracle alone, as in test_str_keys.py: canonical bytes built by
+tests/records_common.py with oracle/pyref.py's typed model and hashed by the C oracle
+(oracle.lift_encoded).
 """
 import bisect
 import ctypes as C
@@ -14,10 +15,14 @@ import functools
 import numpy as np
 import pytest
 
-import test_str_keys as T
-from test_str_keys import TOTALS, KINDS, N_LIFT, canonical, prefix_len, tail_len, fold, agg_int
+import records_common as RC
+from recon_common import DictView, _norm, _outcome, reconcile
+from records_common import (BOUND_KINDS, KINDS, STR_TOTALS as TOTALS, DictModel, agg_int, case_value, fold, ragged_records,
+                            tail_len, to_device)
 
 W = 64
+N_LIFT = 600  # two whole 256-row blocks + an 88-row tail
+prefix_len = functools.partial(RC.prefix_len, "str63")  # (kind, key length)
 SMALL = tuple(range(9))  # values of 0..8 bytes
 QUESTIONS = (1, 32, 33, 64, 65, 200)  # around the one-launch query's 64 and half of it
 
@@ -31,59 +36,17 @@ def schema_of(kind):
 
 @functools.lru_cache(maxsize=None)
 def lift_case(kind, tags=True):
-    """600 records.  Row i's key has i % 64 bytes, but for the rows below: every length 0..63, so
-    every byte alignment and word shift, keys that end at the block edge (56) and past it (57..63),
-    prefixes that end in block 0, at byte 64 and in block 1.  Two present rows carry each TOTALS
-    message length (a row whose prefix is longer than the total takes a key 4, 8, ... bytes shorter),
-    others values of 0..8 bytes, the rest seeded-random lengths in [0, 300).  With tags every 5th
-    row is a tombstone (5 and 64 are coprime: every key length, so messages below, at and above 64
-    bytes), one of them over a non-empty span (ignored)."""
-    from rsos_hip import pack_str_keys
-    n = N_LIFT
-    rng = np.random.default_rng(64000 + sum(kind.encode()) + int(tags))
-    tagged = tags and kind != "plain"
-    tomb = np.array([tagged and i % 5 == 4 for i in range(n)])
-    klen = np.arange(n) % W
-    lens = rng.integers(0, 300, n)
-    present_rows = [i for i in range(n) if not tomb[i]]
-    last = present_rows[-1]
-    # the special rows come from rows 128..: rows 0..127 keep every key length twice among the
-    # present rows, with their random value lengths
-    special = [t for t in TOTALS for _ in range(2)]
-    cand = [i for i in present_rows[:-1] if i >= 128]
-    slots = rng.choice(cand, len(special) + len(SMALL), replace=False)
-    for r, t in zip(slots, special):
-        while prefix_len(kind, int(klen[r])) > t:
-            klen[r] -= 4  # same byte alignment
-        lens[r] = t - prefix_len(kind, int(klen[r]))
-    for r, ln in zip(slots[len(special):], SMALL):
-        lens[r] = ln
-    # a prefix that ends in block 0, at byte 64 and in block 1 (twice), each with no value, a
-    # value that ends inside that block and one that goes on past it
-    taken = set(int(s) for s in slots)
-    for length in (3, 56 - tail_len(kind), 60, 63):
-        rows = [i for i in cand if klen[i] == length and i not in taken][:3]
-        assert len(rows) == 3
-        for r, ln in zip(rows, (0, 5, 100)):
-            lens[r] = ln
-    lens[last] = 37  # the last present record is not empty: it ends the heap
-    if tagged:
-        lens[tomb] = 0
-        lens[9] = 11  # a tombstone over a non-empty span: the span is ignored
-        assert tomb[9]
-    strs = [rng.integers(0, 256, int(k), dtype=np.uint8).tobytes() for k in klen]
-    keys = pack_str_keys(strs, W)
-    phys = rng.integers(0, 1 << 62, n, dtype=np.uint64)
-    logical = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
-    node = rng.integers(0, 1 << 62, n, dtype=np.uint64)
-    values = [rng.integers(0, 256, int(ln), dtype=np.uint8).tobytes() for ln in lens]
-    offsets = np.zeros(n + 1, np.uint64)
-    offsets[1:] = np.cumsum(lens)
-    blobs = [canonical(kind, strs[i], values[i], (int(phys[i]), int(logical[i]), int(node[i])), bool(tomb[i]))
-             for i in range(n)]
-    return {"n": n, "w": W, "keys": keys, "strs": strs, "klen": klen, "phys": phys, "logical": logical,
-            "node": node, "tags": tomb.astype(np.uint8) if tagged else None, "lens": lens,
-            "heap": b"".join(values), "offsets": offsets, "blobs": blobs, "tomb": tomb}
+    """600 records (records_common.build_lift_case).  Row i's key has i % 64 bytes, but for the rows
+    below: every length 0..63, so every byte alignment and word shift, keys that end at the block
+    edge (56) and past it (57..63), prefixes that end in block 0, at byte 64 and in block 1.  Two
+    present rows carry each TOTALS message length, others values of 0..8 bytes; these special rows
+    come from rows 128..: rows 0..127 keep every key length twice among the present rows, with
+    their random value lengths.  A prefix that ends in block 0, at byte 64 and in block 1 (twice)
+    comes with no value, a value that ends inside that block and one that goes on past it.  With
+    tags every 5th row is a tombstone (5 and 64 are coprime: every key length, so messages below,
+    at and above 64 bytes)."""
+    return RC.build_lift_case("str63", "var", kind, tags, N_LIFT, 64000 + sum(kind.encode()) + int(tags), totals=TOTALS,
+                              per_total=2, small=SMALL, slots_from=128, edge_klens=(3, 56 - tail_len(kind), 60, 63))
 
 
 @functools.lru_cache(maxsize=None)
@@ -255,22 +218,10 @@ def test_generated_inputs_cover_the_cases(rsos_hip_lib, kind, tags):
 # ---- GPU: the lift ---------------------------------------------------------------------------------
 
 def check_lift(gpu, kind, tags, lead, slack, keys=None, want=None):
-    from rsos_hip import lift_records
     case = lift_case(kind, tags)
-    want = lift_want(kind, tags) if want is None else want
-    schema = schema_of(kind)
-    cols = T.device_cols(case, schema, gpu, lead, slack, keys=keys)
-    if not slack:  # the first value at heap offset 0, the last record ends at the buffer's end
-        assert cols["values"].numel() == (int(case["offsets"][-1]) + 3) & ~3 and lead == 0
-    fps, bs = lift_records(schema, cols)
-    got, got_bs = fps.cpu().numpy(), bs.cpu().numpy()
-    bad = np.nonzero((got != want).any(axis=1))[0]
-    assert bad.size == 0, (f"{bad.size} rows differ, first {bad[:8]} (key lengths {[len(case['strs'][i]) for i in bad[:8]]}, "
-                           f"message lengths {[len(case['blobs'][i]) for i in bad[:8]]}, "
-                           f"tombstones {[bool(case['tomb'][i]) for i in bad[:8]]})")
-    assert got_bs.shape[0] == (case["n"] + 255) // 256 == 3
-    for g in range(got_bs.shape[0]):
-        assert int.from_bytes(got_bs[g].tobytes(), "little") == fold(want[256 * g:256 * g + 256]), f"block {g}"
+    assert (case["n"] + 255) // 256 == 3
+    RC.check_var_lift(gpu, schema_of(kind), case, lift_want(kind, tags) if want is None else want, lead, slack, keys=keys,
+                      tell=("key lengths", "message lengths", "tombstones"))
 
 
 @pytest.mark.gpu
@@ -302,10 +253,9 @@ def test_padding_and_length_byte_are_not_hashed(gpu, oracle_lib, tight):
         if i % 7 == 3:  # 63 bytes of anything under a length byte no row can hold
             keys[i, :63] = rng.integers(0, 256, 63, dtype=np.uint8)
             keys[i, 63] = {3: 64, 10: 255}.get(i, 64 + (i * 37) % 192)
-            v = case["heap"][int(case["offsets"][i]):int(case["offsets"][i + 1])]
-            blobs.append(canonical("dated", keys[i, :63].tobytes(), b"" if case["tomb"][i] else v,
-                                   (int(case["phys"][i]), int(case["logical"][i]), int(case["node"][i])),
-                                   bool(case["tomb"][i])))
+            blobs.append(RC.canonical("str63", "var", "dated", keys[i, :63].tobytes(), case_value(case, i),
+                                      (int(case["phys"][i]), int(case["logical"][i]), int(case["node"][i])),
+                                      bool(case["tomb"][i])))
     assert {int(keys[i, 63]) for i in clipped} >= {64, 255} and any(case["tomb"][i] for i in clipped)
     want[clipped] = O.lift_encoded(blobs, threads=4)
     assert (keys != case["keys"]).any(axis=1).sum() >= case["n"] - 10
@@ -318,25 +268,19 @@ def test_dual_lift_equals_the_two_single_lifts(gpu, oracle_lib):
     from rsos_hip import lift_dual, lift_records
     case = lift_case("dated")
     schema = schema_of("dated")
-    cols = T.device_cols(case, schema, gpu, 5, 64)
+    cols = RC.device_cols(case, schema, gpu, 5, 64)
     fd, bd, fp, bp = lift_dual(schema, cols)
     f1, b1 = lift_records(schema, cols)
     f2, b2 = lift_records(schema_of("projection"), {k: v for k, v in cols.items() if k not in ("phys", "logical", "node")})
     for a, b in ((fd, f1), (bd, b1), (fp, f2), (bp, b2)):
         assert np.array_equal(a.cpu().numpy(), b.cpu().numpy())
     assert np.array_equal(f1.cpu().numpy(), lift_want("dated"))
-    blobs = [canonical("projection", case["strs"][i],
-                       case["heap"][int(case["offsets"][i]):int(case["offsets"][i + 1])], tomb=bool(case["tomb"][i]))
+    blobs = [RC.canonical("str63", "var", "projection", case["strs"][i], case_value(case, i), tomb=bool(case["tomb"][i]))
              for i in range(case["n"])]
     assert np.array_equal(fp.cpu().numpy(), O.lift_encoded(blobs, threads=4))
 
 
 # ---- GPU: the store against a model ----------------------------------------------------------------
-
-class Model(T.Model):
-    """string -> (record, oracle fingerprint) for a str63 dated var store."""
-    W = 64
-
 
 PREFIX56 = b"production-eu-west-1/ReplicaSet/frontend-web-7c9d8b6f54-" .ljust(56, b"x")
 assert len(PREFIX56) == 56
@@ -371,22 +315,11 @@ def string_pool(rng, n):
     return list(pool)
 
 
-def to_device(cols, gpu):
-    import torch
-    heap = np.zeros((cols["values"].size + 3) & ~3, np.uint8)
-    heap[:cols["values"].size] = cols["values"]
-    return {"keys": torch.from_numpy(cols["keys"].copy()).to(gpu), "phys": torch.from_numpy(cols["phys"].view(np.int64)).to(gpu),
-            "logical": torch.from_numpy(cols["logical"].view(np.int32)).to(gpu),
-            "node": torch.from_numpy(cols["node"].view(np.int64)).to(gpu), "tags": torch.from_numpy(cols["tags"]).to(gpu),
-            "values": torch.from_numpy(heap).to(gpu),
-            "value_offsets": torch.from_numpy(cols["value_offsets"].astype(np.int64)).to(gpu)}
-
-
 def check_questions(st, m):
     """ranks, selects and key dumps of 1 .. 200 questions (the one-launch query holds 64 keys of at
     most 32 bytes) and key-range aggregates over every pair of bound kinds."""
     from rsos_hip import pack_str_keys, _abi as A
-    from rsos_hip.store import KeyRange, _np_ptr
+    from rsos_hip.store import _np_ptr
     ks = sorted(m.rows)
     n = len(ks)
     fps = [m.rows[k][1] for k in ks]
@@ -403,16 +336,9 @@ def check_questions(st, m):
         assert buf.tobytes() == pack_str_keys(ks[lo:lo + q], 64).tobytes(), q
         for r in {0, q - 1, n - q, n - 1}:
             assert st.select(r) == ks[r]
-    kinds = ("unbounded", "included", "excluded")
     probes = [ks[i] for i in range(0, n, n // 7)] + [PREFIX56 + b"\x80", b"pod/web" + b"\0" * 20, b"pod/web\0\x01"]
-    for i, (lk, hk) in enumerate((a, b) for a in kinds for b in kinds):
-        a, b = sorted((probes[(i * 3) % len(probes)], probes[(i * 5 + 4) % len(probes)]))
-        rg = KeyRange(None if lk == "unbounded" else a, None if hk == "unbounded" else b, lk, hk)
-        inside = [j for j, k in enumerate(ks)
-                  if (lk == "unbounded" or k > a or (lk == "included" and k == a))
-                  and (hk == "unbounded" or k < b or (hk == "included" and k == b))]
-        got = st.aggregate(rg)
-        assert (got.size, agg_int(got)) == (len(inside), fold(fps[j] for j in inside)), (lk, hk, a, b)
+    RC.check_key_ranges(st, ks, fps, ((lk, hk, *sorted((probes[(i * 3) % len(probes)], probes[(i * 5 + 4) % len(probes)])))
+                                      for i, (lk, hk) in enumerate((a, b) for a in BOUND_KINDS for b in BOUND_KINDS)))
 
 
 @pytest.mark.gpu
@@ -434,8 +360,8 @@ def test_store_against_model(gpu, oracle_lib, tier):
     fresh = pool[1200:]
     absent = fresh[900:920] + [PREFIX56, PREFIX56 + b"\0", b"pod/web\0\x01", b"pod/wea" + b"\xff" * 56, b"\xff" * 63]
     schema = RecordSchema.dated("str63", "var")
-    st, m = GpuFingerprintStore(schema, host_tier=tier), Model()
-    recs = T.ragged_records(rng, base, long_every=150)
+    st, m = GpuFingerprintStore(schema, host_tier=tier), DictModel("str63", "var")
+    recs = ragged_records(rng, base, long_every=150)
     st.load_bulk(m.cols(recs))
     m.apply(recs, [0] * len(recs))
     m.check(st, absent)
@@ -446,7 +372,7 @@ def test_store_against_model(gpu, oracle_lib, tier):
     # and deletes of loaded keys (deep ones among them), shuffled
     ow = [base[i] for i in rng.choice(len(base), 300, replace=False)]
     new = deep[300:2800] + zeros[1::2] + fresh[:100]
-    batch = T.ragged_records(rng, new + ow[:150], long_every=400) + [(k, (0, 0, 0), 0, b"") for k in ow[150:]]
+    batch = ragged_records(rng, new + ow[:150], long_every=400) + [(k, (0, 0, 0), 0, b"") for k in ow[150:]]
     ops = [0] * (len(new) + 150) + [1] * 150
     perm = rng.permutation(len(batch))
     batch, ops = [batch[i] for i in perm], [ops[i] for i in perm]
@@ -460,7 +386,7 @@ def test_store_against_model(gpu, oracle_lib, tier):
     assert (st.size(), agg_int(st.aggregate())) == (len(m.rows), root)
 
     again = fresh[100]
-    staged = T.ragged_records(rng, [again] + fresh[101:125] + [again] + ow[:23] + [again], long_every=25)
+    staged = ragged_records(rng, [again] + fresh[101:125] + [again] + ow[:23] + [again], long_every=25)
     sops = [0] * 50
     for j in (5, 30, 31):
         sops[j] = 1
@@ -470,7 +396,7 @@ def test_store_against_model(gpu, oracle_lib, tier):
     m.check(st, absent)  # the first question flushes
     assert m.rows[again][0][3] == staged[-1][3]
 
-    dev = T.ragged_records(rng, fresh[200:264] + deep[2800:2900] + ow[40:104], long_every=16)
+    dev = ragged_records(rng, fresh[200:264] + deep[2800:2900] + ow[40:104], long_every=16)
     dops = np.zeros(len(dev), np.uint8)
     dops[70:80] = 1  # deletes of keys the store does not hold
     n_new = 64 + 100 - 10
@@ -478,8 +404,8 @@ def test_store_against_model(gpu, oracle_lib, tier):
     m.apply(dev, dops.tolist())
     m.check(st, absent)
 
-    q1 = T.ragged_records(rng, fresh[300:400] + deep[2900:2950], long_every=30)
-    q2 = T.ragged_records(rng, fresh[380:480] + deep[2940:3000] + ow[150:170], long_every=30)  # overlaps q1, re-inserts deleted keys
+    q1 = ragged_records(rng, fresh[300:400] + deep[2900:2950], long_every=30)
+    q2 = ragged_records(rng, fresh[380:480] + deep[2940:3000] + ow[150:170], long_every=30)  # overlaps q1, re-inserts deleted keys
     want2 = (sum(1 for r in q2 if r[0] not in m.rows and r[0] not in {x[0] for x in q1}),
              sum(1 for r in q2 if r[0] in m.rows or r[0] in {x[0] for x in q1}), 0)
     assert st.apply_device_many([to_device(m.cols(q1), gpu), to_device(m.cols(q2), gpu)]) == [(150, 0, 0), want2]
@@ -493,7 +419,7 @@ def test_store_against_model(gpu, oracle_lib, tier):
     check_questions(st, m)
     assert st.batch_stats()["small"] == 0
 
-    good = m.cols(T.ragged_records(rng, fresh[500:510]))
+    good = m.cols(ragged_records(rng, fresh[500:510]))
     bads = []
     k = good["keys"].copy()
     k[3, 63] = 64  # a length byte no 64-byte row can hold
@@ -527,7 +453,7 @@ def recon_sides():
     special = {stem, stem + b"\0", stem + b"z", d7 + b"0", d7 + b"1"}
     pool = [s for s in pool if s not in special]
     rng.shuffle(pool)
-    shared = [(k, s, 0, v) for k, s, _, v in T.ragged_records(rng, sorted(pool[:2996]), long_every=300)]
+    shared = [(k, s, 0, v) for k, s, _, v in ragged_records(rng, sorted(pool[:2996]), long_every=300)]
     a_recs, b_recs = list(shared), list(shared)
     for j, extra in ((321, b"\0"), (2222, b"changed")):
         ch = shared[j]
@@ -541,7 +467,7 @@ def recon_sides():
     models = []
     for recs in (a_recs, b_recs):
         recs.sort(key=lambda r: r[0])
-        m = Model()
+        m = DictModel("str63", "var")
         m.apply(recs, [0] * len(recs))
         models.append((recs, m))
     return models, want
@@ -567,10 +493,11 @@ def test_reconciliation_matches_the_literal_driver(gpu, oracle_lib, policy, tier
     a, b = stores
     assert a.size() == b.size() == 3000
     pol, decide = {"fixed16": (R.FixedFanOut(16), OR.fixed_fan_out(16)), "sqrt": (R.SqrtFanOut(), OR.sqrt_fan_out)}[policy]
-    want_log, _ = T.reconcile(T.DictView(ma), T.DictView(mb),
-                              lambda v, act, ch, en: OR.protocol_round(v, decide, act, ch, en), OR.initial_ranges)
-    got_log, ranges = T.reconcile(a, b, lambda v, act, ch, en: T._outcome(R.protocol_round_with_policy(v, pol, act, ch, en)),
-                                  R.initial_ranges)
+    want_log = reconcile(DictView(ma), DictView(mb), lambda v, act, ch, en: OR.protocol_round(v, decide, act, ch, en),
+                         OR.initial_ranges, max_rounds=100)[0]
+    got_log, ea, eb = reconcile(a, b, lambda v, act, ch, en: _outcome(R.protocol_round_with_policy(v, pol, act, ch, en)),
+                                R.initial_ranges, max_rounds=100)
+    ranges = ea + eb
     assert len(got_log) == len(want_log) > 2
     for (gc, ge, go), (wc, we, wo) in zip(got_log, want_log):
         assert go == wo and ge == we and gc == wc
@@ -588,7 +515,7 @@ def test_reconciliation_matches_the_literal_driver(gpu, oracle_lib, policy, tier
     active, k = R.initial_segments(a), 0
     while len(active):
         ch, en, o = R.protocol_round_segments((b, a)[k % 2], pol, active)
-        assert T._outcome(o) == want_log[k][2] and T._norm(ch.items(schema)) == want_log[k][0]
+        assert _outcome(o) == want_log[k][2] and _norm(ch.items(schema)) == want_log[k][0]
         items = ch.items(schema)
         data = wire.encode(schema, items, key_form="vec", msg_tag=wire.COMPARISON_ITEM)
         back, used = wire.decode_stream(schema, data, len(items), key_form="vec", msg_tag=wire.COMPARISON_ITEM)
@@ -632,7 +559,7 @@ def test_fingerprint_map_with_string_keys(gpu, oracle_lib):
 
     def fp(k):
         v, stamp, tomb = model[k]
-        return O.lift_encoded([canonical("dated", k.encode(), v.encode(), stamp, tomb)])[0].tobytes()
+        return O.lift_encoded([RC.canonical("str63", "var", "dated", k.encode(), v.encode(), stamp, tomb)])[0].tobytes()
     order = sorted(model, key=str.encode)
     agg = fm.aggregate()
     assert (agg.size, agg_int(agg)) == (len(model), fold(fp(k) for k in order))

@@ -3,9 +3,9 @@
 (rsos/src/fingerprint_tree_map/tests/basic.rs:205,226), ReplicatedSet<String> = ReplicatedMap<String, ()>
 (src/replicated_set.rs:56), String -> u64 counters.
 
-Expected fingerprints come from the oracle alone: every record's canonical bytes are built here
-with oracle/pyref.py's typed model (Str, U32 / U64 / Unit, timestamp, present, TOMBSTONE, entry) and
-hashed by the C oracle (oracle.lift_encoded) -- never by the product's encoder or a second GPU kernel.
+Expected fingerprints come from the oracle alone: every record's canonical bytes are built by
+tests/records_common.py with oracle/pyref.py's typed model and hashed by the C oracle
+(oracle.lift_encoded) -- never by the product's encoder or a second GPU kernel.
 """
 import bisect
 import ctypes as C
@@ -14,13 +14,14 @@ import functools
 import numpy as np
 import pytest
 
-import pyref as P  # oracle/pyref.py
-from test_str_keys import _outcome, agg_int, fold, reconcile
+import records_common as RC
+from recon_common import _outcome, reconcile
+from records_common import BOUND_KINDS, KINDS, DictModel, agg_int, fold, host_cols, to_device, value_column
 
 WIDTHS = (16, 32, 64)
 VALUES = ("unit", "u32", "u64")
-KINDS = ("plain", "dated", "projection")
-VBYTES = {"unit": 0, "u32": 4, "u64": 8}
+VBYTES = {vk: RC.val_width(vk) for vk in VALUES}
+STR = "str63"  # for canonical() and msg_len(): they take the string, whatever row it travels in
 N_LIFT = 600  # two whole 256-row blocks + an 88-row tail
 SHAPES = [("plain", False), ("dated", True), ("dated", False), ("projection", True), ("projection", False)]
 SHAPE_IDS = ["plain", "dated-tags", "dated-untagged", "projection-tags", "projection-untagged"]
@@ -31,89 +32,27 @@ def schema_of(w, vk, kind):
     return getattr(RecordSchema, kind)(f"str{w - 1}", vk)
 
 
-def typed(vk, v):
-    return P.Unit() if vk == "unit" else P.U32(v) if vk == "u32" else P.U64(v)
-
-
-def canonical(kind, vk, key: bytes, value=0, stamp=(0, 0, 0), tomb=False) -> bytes:
-    """encode_to_vec(&k) ++ encode_to_vec(&v) by the oracle's typed model: the key is the *string*
-    (u64 length, then its bytes), whatever row it travels in."""
-    state = P.TOMBSTONE if tomb else P.present(typed(vk, value))
-    if kind == "plain":
-        assert not tomb
-        v = typed(vk, value)
-    elif kind == "dated":
-        v = P.entry(P.timestamp(*stamp), state)
-    else:
-        v = state
-    return P.encode(P.Str(key)) + P.encode(v)
-
-
 def msg_len(kind, vk, klen, tomb=False):
-    tail = (20 if kind == "dated" else 0) + (0 if kind == "plain" else 4)
-    return 8 + klen + tail + (0 if tomb else VBYTES[vk])
-
-
-def value_column(vk, vals):
-    """n rows of the value column (uint8, n x 0 / 4 / 8), little-endian."""
-    if vk == "unit":
-        return None
-    return np.array(vals, np.uint64).astype({"u32": "<u4", "u64": "<u8"}[vk]).view(np.uint8).reshape(len(vals), VBYTES[vk])
+    return RC.msg_len(STR, vk, kind, klen, tomb=tomb)
 
 
 # ---- the lift's inputs ----------------------------------------------------------------------------
 
 @functools.lru_cache(maxsize=None)
 def lift_case(w, vk, kind, tags=True):
-    """600 records of one shape.  Row i's key has i % w random bytes.  With tags every 5th row is a
-    tombstone: gcd(w, 5) = 1, so every key length occurs both present and as a tombstone within
-    5 w <= 320 rows.  Values are seeded-random with 0, 2^32 - 1 and 2^64 - 1 (masked to the value's
-    width) among the first rows; a tombstone's value row is nonzero and ignored."""
-    from rsos_hip import pack_str_keys
-    n = N_LIFT
-    rng = np.random.default_rng(7000 * w + 100 * VBYTES[vk] + sum(kind.encode()) + int(tags))
-    tagged = tags and kind != "plain"
-    tomb = np.array([tagged and i % 5 == 4 for i in range(n)])
-    klen = np.arange(n) % w
-    mask = (1 << (8 * VBYTES[vk])) - 1
-    vals = [int(x) & mask for x in rng.integers(0, 1 << 63, n, dtype=np.uint64) * 2 + 1]  # odd: nonzero
-    for row, v in ((0, 0), (1, (1 << 32) - 1), (2, (1 << 64) - 1), (5, 0), (6, (1 << 64) - 1)):
-        assert not tomb[row]
-        vals[row] = v & mask
-    strs = [rng.integers(0, 256, int(k), dtype=np.uint8).tobytes() for k in klen]
-    phys = rng.integers(0, 1 << 62, n, dtype=np.uint64)
-    logical = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
-    node = rng.integers(0, 1 << 62, n, dtype=np.uint64)
-    blobs = [canonical(kind, vk, strs[i], vals[i], (int(phys[i]), int(logical[i]), int(node[i])), bool(tomb[i]))
-             for i in range(n)]
-    return {"n": n, "w": w, "keys": pack_str_keys(strs, w), "strs": strs, "phys": phys, "logical": logical,
-            "node": node, "tags": tomb.astype(np.uint8) if tagged else None, "vals": vals,
-            "values": value_column(vk, vals), "blobs": blobs, "tomb": tomb}
+    """600 records of one shape (records_common.build_lift_case).  Row i's key has i % w random
+    bytes.  With tags every 5th row is a tombstone: gcd(w, 5) = 1, so every key length occurs both
+    present and as a tombstone within 5 w <= 320 rows.  Values are seeded-random with 0, 2^32 - 1
+    and 2^64 - 1 (masked to the value's width) among the first rows."""
+    return RC.build_lift_case(f"str{w - 1}", vk, kind, tags, N_LIFT,
+                              7000 * w + 100 * VBYTES[vk] + sum(kind.encode()) + int(tags),
+                              edge_vals=((0, 0), (1, (1 << 32) - 1), (2, (1 << 64) - 1), (5, 0), (6, (1 << 64) - 1)))
 
 
 @functools.lru_cache(maxsize=None)
 def lift_want(w, vk, kind, tags=True):
     import oracle as O
     return O.lift_encoded(lift_case(w, vk, kind, tags)["blobs"], threads=4)
-
-
-def host_cols(case, schema, n=None, keys=None):
-    n = case["n"] if n is None else n
-    cols = {"keys": (case["keys"] if keys is None else keys)[:n].copy()}  # (copies: the case is shared)
-    if case["values"] is not None:
-        cols["values"] = case["values"][:n].copy()
-    if schema.dated_kind:
-        cols.update(phys=case["phys"][:n].copy(), logical=case["logical"][:n].copy(), node=case["node"][:n].copy())
-    if case["tags"] is not None:
-        cols["tags"] = case["tags"][:n].copy()
-    return cols
-
-
-def to_device(cols, dev):
-    import torch
-    view = {"phys": np.int64, "logical": np.int32, "node": np.int64}
-    return {k: torch.from_numpy(np.ascontiguousarray(v).view(view.get(k, v.dtype))).to(dev)
-            for k, v in cols.items() if v is not None}
 
 
 # ---- CPU ------------------------------------------------------------------------------------------
@@ -207,16 +146,8 @@ def test_generated_inputs_cover_the_cases(rsos_hip_lib, w):
 # ---- GPU: the lift ---------------------------------------------------------------------------------
 
 def check_lift(gpu, schema, case, want, n):
-    from rsos_hip import lift_records
-    fps, bs = lift_records(schema, to_device(host_cols(case, schema, n), gpu))
-    got, got_bs = fps.cpu().numpy(), bs.cpu().numpy()
-    bad = np.nonzero((got != want[:n]).any(axis=1))[0]
-    assert bad.size == 0, (f"n = {n}: {bad.size} rows differ, first {bad[:8]} (key lengths "
-                           f"{[len(case['strs'][i]) for i in bad[:8]]}, message lengths "
-                           f"{[len(case['blobs'][i]) for i in bad[:8]]}, tombstones {[bool(case['tomb'][i]) for i in bad[:8]]})")
-    assert got_bs.shape[0] == (n + 255) // 256
-    for g in range(got_bs.shape[0]):
-        assert int.from_bytes(got_bs[g].tobytes(), "little") == fold(want[256 * g:min(256 * g + 256, n)]), (n, g)
+    RC.check_lift(schema, to_device(host_cols(case, schema, n), gpu), case, want, n,
+                  tell=("key lengths", "message lengths", "tombstones"))
 
 
 @pytest.mark.gpu
@@ -240,7 +171,7 @@ def test_dual_lift_equals_both_single_oracles(gpu, oracle_lib, w, vk):
     case = lift_case(w, vk, "dated")
     fd, bd, fp, bp = lift_dual(schema_of(w, vk, "dated"), to_device(host_cols(case, schema_of(w, vk, "dated")), gpu))
     want_d = lift_want(w, vk, "dated")
-    want_p = O.lift_encoded([canonical("projection", vk, case["strs"][i], case["vals"][i], tomb=bool(case["tomb"][i]))
+    want_p = O.lift_encoded([RC.canonical(STR, vk, "projection", case["strs"][i], case["vals"][i], tomb=bool(case["tomb"][i]))
                              for i in range(case["n"])], threads=4)
     assert np.array_equal(fd.cpu().numpy(), want_d) and np.array_equal(fp.cpu().numpy(), want_p)
     for got, want in ((bd, want_d), (bp, want_p)):
@@ -265,7 +196,7 @@ def test_malformed_device_rows_are_clipped_and_masked(gpu, oracle_lib, w):
             if i % 7 == 3:
                 keys[i, :w - 1] = rng.integers(0, 256, w - 1, dtype=np.uint8)
                 keys[i, w - 1] = 200
-                blobs.append(canonical(kind, vk, keys[i, :w - 1].tobytes(), case["vals"][i],
+                blobs.append(RC.canonical(STR, vk, kind, keys[i, :w - 1].tobytes(), case["vals"][i],
                                        (int(case["phys"][i]), int(case["logical"][i]), int(case["node"][i])),
                                        bool(case["tomb"][i])))
         assert kind == "plain" or any(case["tomb"][i] for i in clipped)
@@ -314,7 +245,7 @@ def test_string_store_hashes_the_string_not_the_row(gpu, oracle_lib, vk):
         if vk == "u64":
             c["values"] = value_column(vk, vals[lo:hi])
         return c
-    want = O.lift_encoded([canonical("plain", vk, s, v) for s, v in zip(strs, vals)])
+    want = O.lift_encoded([RC.canonical(STR, vk, "plain", s, v) for s, v in zip(strs, vals)])
     roots = {}
     for name in ("str15", "bytes16"):
         st = GpuFingerprintStore(RecordSchema.plain(name, vk), host_tier=False)
@@ -332,54 +263,25 @@ def test_string_store_hashes_the_string_not_the_row(gpu, oracle_lib, vk):
 
 # ---- GPU: the store against a dict model -----------------------------------------------------------
 
-class Model:
+class Model(DictModel):
     """string -> (record, oracle fingerprint); a record is (key, (phys, logical, node), tomb, value)."""
 
     def __init__(self, w, vk, kind):
-        self.w, self.vk, self.kind, self.rows = w, vk, kind, {}
-
-    def cols(self, recs):
-        from rsos_hip import pack_str_keys
-        c = {"keys": pack_str_keys([r[0] for r in recs], self.w)}
-        if self.vk != "unit":
-            c["values"] = value_column(self.vk, [r[3] for r in recs])
-        if self.kind == "dated":
-            c.update(phys=np.array([r[1][0] for r in recs], np.uint64), logical=np.array([r[1][1] for r in recs], np.uint32),
-                     node=np.array([r[1][2] for r in recs], np.uint64))
-        if self.kind != "plain":
-            c["tags"] = np.array([r[2] for r in recs], np.uint8)
-        return c
-
-    def apply(self, recs, ops):
-        """The batch in order (a key met twice keeps its last row), fingerprints from the oracle."""
-        import oracle as O
-        ins = [r for r, op in zip(recs, ops) if op == 0]
-        fps = iter(O.lift_encoded([canonical(self.kind, self.vk, r[0], r[3], r[1], bool(r[2])) for r in ins]))
-        for r, op in zip(recs, ops):
-            if op == 0:
-                self.rows[r[0]] = (r, next(fps).tobytes())
-            else:
-                self.rows.pop(r[0], None)
+        super().__init__(f"str{w - 1}", vk, kind)
+        self.vk = vk
 
     def check(self, st):
         """len and root, aggregate_keys over all nine bound-kind pairs, ranks / select / keys, and
         that no batch took the small path."""
         from rsos_hip import pack_str_keys, _abi as A
-        from rsos_hip.store import KeyRange, _np_ptr
+        from rsos_hip.store import _np_ptr
         ks = sorted(self.rows)
         n, fps = len(ks), [self.rows[k][1] for k in ks]
         assert st.size() == n
         assert agg_int(st.aggregate()) == fold(fps)
         probes = [ks[i] for i in range(0, n, max(n // 9, 1))] + [b"", b"\xff" * (self.w - 1), b"no such key"[:self.w - 1]]
-        kinds = ("unbounded", "included", "excluded")
-        for i, (lk, hk) in enumerate((a, b) for a in kinds for b in kinds):
-            a, b = sorted((probes[(i * 3) % len(probes)], probes[(i * 5 + 4) % len(probes)]))
-            rg = KeyRange(None if lk == "unbounded" else a, None if hk == "unbounded" else b, lk, hk)
-            inside = [j for j, k in enumerate(ks)
-                      if (lk == "unbounded" or k > a or (lk == "included" and k == a))
-                      and (hk == "unbounded" or k < b or (hk == "included" and k == b))]
-            got = st.aggregate(rg)
-            assert (got.size, agg_int(got)) == (len(inside), fold(fps[j] for j in inside)), (lk, hk, a, b)
+        RC.check_key_ranges(st, ks, fps, ((lk, hk, *sorted((probes[(i * 3) % len(probes)], probes[(i * 5 + 4) % len(probes)])))
+                                          for i, (lk, hk) in enumerate((a, b) for a in BOUND_KINDS for b in BOUND_KINDS)))
         asked = probes + [k + b"\x01" for k in probes if len(k) < self.w - 1]
         assert st.ranks(pack_str_keys(asked, self.w)).tolist() == [bisect.bisect_left(ks, k) for k in asked]
         for r in (0, 1, n // 2, n - 1):
@@ -539,8 +441,9 @@ def test_reconciliation_converges(gpu, oracle_lib, tier):
     (a, b), (ma, mb) = stores, models
     assert agg_int(a.aggregate()) == fold(v[1] for v in ma.rows.values()) != agg_int(b.aggregate())
     pol = R.FixedFanOut(16)
-    log, ranges = reconcile(a, b, lambda v, act, ch, en: _outcome(R.protocol_round_with_policy(v, pol, act, ch, en)),
-                            R.initial_ranges)
+    log, ea, eb = reconcile(a, b, lambda v, act, ch, en: _outcome(R.protocol_round_with_policy(v, pol, act, ch, en)),
+                            R.initial_ranges, max_rounds=100)
+    ranges = ea + eb
     assert len(log) > 2
 
     def inside(key):
@@ -659,7 +562,7 @@ def test_fingerprint_map_with_string_keys_and_fixed_values(gpu, oracle_lib):
     assert fm.delete("a") == b"" and fm.delete("a") is None
     left = sorted((k for k in names if k != "a"), key=str.encode)
     agg = fm.aggregate()
-    assert (agg.size, agg_int(agg)) == (5, fold(O.lift_encoded([canonical("plain", "unit", k.encode()) for k in left])))
+    assert (agg.size, agg_int(agg)) == (5, fold(O.lift_encoded([RC.canonical(STR, "unit", "plain", k.encode(), None) for k in left])))
     assert [k for k, _ in fm.enumerate()] == left
     fm.close()
     fm = FingerprintMap(RecordSchema.plain("str15", "u32"))
@@ -669,7 +572,7 @@ def test_fingerprint_map_with_string_keys_and_fixed_values(gpu, oracle_lib):
     assert fm.insert("hello", 8) == 7
     model["hello"] = 8
     agg = fm.aggregate()
-    assert (agg.size, agg_int(agg)) == (4, fold(O.lift_encoded([canonical("plain", "u32", k.encode(), v) for k, v in model.items()])))
+    assert (agg.size, agg_int(agg)) == (4, fold(O.lift_encoded([RC.canonical(STR, "u32", "plain", k.encode(), v) for k, v in model.items()])))
     with pytest.raises(ValueError):
         fm.insert("sixteen bytes...", 1)
     fm.close()
@@ -679,7 +582,7 @@ def test_fingerprint_map_with_string_keys_and_fixed_values(gpu, oracle_lib):
     for k, e in rows.items():
         fm.insert(k, e)
     agg = fm.aggregate()
-    want = O.lift_encoded([canonical("dated", "u64", k.encode(), e.value, (e.phys, e.logical, e.node), e.tombstone)
+    want = O.lift_encoded([RC.canonical(STR, "u64", "dated", k.encode(), e.value, (e.phys, e.logical, e.node), e.tombstone)
                            for k, e in rows.items()])
     assert (agg.size, agg_int(agg)) == (4, fold(want))
     assert fm.store.batch_stats()["small"] == 0

@@ -3,9 +3,9 @@
 (RH_VAL_VARBYTES) -- the reference's own example map, ReplicatedMap<String, String>
 (examples/k8s/main.rs:53).
 
-Expected fingerprints come from the oracle alone: every record's canonical bytes are built here
-with oracle/pyref.py's typed model (Str, timestamp, present, TOMBSTONE, entry) and hashed by the C
-oracle (oracle.lift_encoded) -- never by the product's encoder or a second GPU kernel.
+Expected fingerprints come from the oracle alone: every record's canonical bytes are built by
+tests/records_common.py with oracle/pyref.py's typed model and hashed by the C oracle
+(oracle.lift_encoded) -- never by the product's encoder or a second GPU kernel.
 """
 import ctypes as C
 import functools
@@ -14,14 +14,12 @@ import numpy as np
 import pytest
 
 import pyref as P  # oracle/pyref.py
+import records_common as RC
+from recon_common import DictView, _norm, _outcome, reconcile
+from records_common import KINDS, STR_TOTALS as TOTALS, DictModel, agg_int, case_value, fold, ragged_records
 
-MOD = 1 << 256
-# message lengths (prefix + value) among the present rows: block edges, the chunk edge, and the
-# multi-chunk kernel with parent nodes (two, three and five chunks)
-TOTALS = (63, 64, 65, 127, 128, 129, 1023, 1024, 1025, 1500, 3000, 5000)
 SMALL = (0, 1, 2, 3, 4, 5, 7, 8)
 WIDTHS = (16, 32)
-KINDS = ("plain", "dated", "projection")
 N_LIFT = 600  # two whole 256-row blocks + an 88-row tail
 
 # the order test's fixed strings: prefix families over the padding byte, the longest strings
@@ -38,105 +36,25 @@ def schema_of(w, kind):
     return getattr(RecordSchema, kind)(key_name(w), "var")
 
 
-def tail_len(kind):
-    """The fields between the key and the value's bytes: stamp, State variant, u64 value length."""
-    return (20 if kind == "dated" else 0) + (0 if kind == "plain" else 4) + 8
-
-
-def prefix_len(kind, klen):
-    return 8 + klen + tail_len(kind)
-
-
-def canonical(kind, key: bytes, value: bytes, stamp=(0, 0, 0), tomb=False) -> bytes:
-    """rsos::encoding::encode_to_vec(&k) ++ encode_to_vec(&v) by the oracle's typed model: the key
-    is the *string* (u64 length, then its bytes), whatever row it travels in."""
-    state = P.TOMBSTONE if tomb else P.present(P.Str(value))
-    if kind == "plain":
-        assert not tomb
-        v = P.Str(value)
-    elif kind == "dated":
-        v = P.entry(P.timestamp(*stamp), state)
-    else:
-        v = state
-    return P.encode(P.Str(key)) + P.encode(v)
-
-
-def fold(fps) -> int:
-    return sum(int.from_bytes(bytes(f), "little") for f in fps) % MOD
-
-
-def agg_int(a) -> int:
-    return a.fingerprint.to_int()
+tail_len = RC.tail_len
+prefix_len = functools.partial(RC.prefix_len, "str31")  # (kind, key length): the width does not enter
 
 
 @functools.lru_cache(maxsize=None)
 def lift_case(w, kind, tags=True):
-    """600 records of one shape.  Row i's key has i % w bytes, but for a few rows below (every
-    length 0..w-1: all four byte alignments of the fields behind it, every word shift).  Values
-    are packed back to back.  Two present rows carry each TOTALS message length (value length = total - prefix of that row's
-    key), others the SMALL lengths, the rest seeded-random lengths in [0, 300).  With tags every
-    5th row is a tombstone, one of them over a non-empty span (ignored)."""
-    from rsos_hip import pack_str_keys
-    n = N_LIFT
-    rng = np.random.default_rng(1000 * w + sum(kind.encode()) + int(tags))
-    tagged = tags and kind != "plain"
-    tomb = np.array([tagged and i % 5 == 4 for i in range(n)])
-    klen = np.arange(n) % w
-    lens = rng.integers(0, 300, n)
-    present_rows = [i for i in range(n) if not tomb[i]]
-    last = present_rows[-1]  # (row 599 is a tombstone of the tagged kinds)
-    special = [t for t in TOTALS for _ in range(2)]
-    slots = rng.choice(present_rows[:-1], len(special) + len(SMALL), replace=False)
-    for r, t in zip(slots, special):
-        # a row whose prefix is longer than the total (63 against 71) takes a shorter key instead
-        while prefix_len(kind, int(klen[r])) > t:
-            klen[r] -= 4  # same byte alignment
-        lens[r] = t - prefix_len(kind, int(klen[r]))
-    for r, ln in zip(slots[len(special):], SMALL):
-        lens[r] = ln
-    lens[last] = 37  # the last present record is not empty: it ends the heap
-    if tagged:
-        lens[tomb] = 0
-        lens[9] = 11  # a tombstone over a non-empty span: the span is ignored
-        assert tomb[9]
-    strs = [rng.integers(0, 256, int(k), dtype=np.uint8).tobytes() for k in klen]
-    keys = pack_str_keys(strs, w)
-    phys = rng.integers(0, 1 << 62, n, dtype=np.uint64)
-    logical = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
-    node = rng.integers(0, 1 << 62, n, dtype=np.uint64)
-    values = [rng.integers(0, 256, int(ln), dtype=np.uint8).tobytes() for ln in lens]
-    offsets = np.zeros(n + 1, np.uint64)
-    offsets[1:] = np.cumsum(lens)
-    blobs = [canonical(kind, strs[i], values[i], (int(phys[i]), int(logical[i]), int(node[i])), bool(tomb[i]))
-             for i in range(n)]
-    return {"n": n, "w": w, "keys": keys, "strs": strs, "klen": klen, "phys": phys, "logical": logical,
-            "node": node, "tags": tomb.astype(np.uint8) if tagged else None, "lens": lens,
-            "heap": b"".join(values), "offsets": offsets, "blobs": blobs, "tomb": tomb}
+    """600 records of one shape (records_common.build_lift_case).  Row i's key has i % w bytes, but
+    for a few rows below (every length 0..w-1: all four byte alignments of the fields behind it,
+    every word shift).  Two present rows carry each TOTALS message length (a row whose prefix is
+    longer than the total, 63 against 71, takes a shorter key instead), others the SMALL lengths.
+    (Row 599 is a tombstone of the tagged kinds.)"""
+    return RC.build_lift_case(key_name(w), "var", kind, tags, N_LIFT, 1000 * w + sum(kind.encode()) + int(tags),
+                              totals=TOTALS, per_total=2, small=SMALL)
 
 
 @functools.lru_cache(maxsize=None)
 def lift_want(w, kind, tags=True):
     import oracle as O
     return O.lift_encoded(lift_case(w, kind, tags)["blobs"], threads=4)
-
-
-def device_cols(case, schema, dev, lead=0, slack=0, keys=None):
-    """The case as device columns; the heap is `lead` bytes of filler, the values, `slack` bytes
-    of filler, then filler up to a multiple of 4 (0xA5: a byte read past a value would show)."""
-    import torch
-    used = lead + len(case["heap"]) + slack
-    heap = np.full((used + 3) & ~3, 0xA5, np.uint8)
-    heap[lead:lead + len(case["heap"])] = np.frombuffer(case["heap"], np.uint8)
-    cols = {"values": torch.from_numpy(heap).to(dev),
-            "value_offsets": torch.from_numpy((case["offsets"] + np.uint64(lead)).astype(np.int64)).to(dev),
-            "keys": torch.from_numpy(np.ascontiguousarray(case["keys"] if keys is None else keys)).to(dev)}
-    if schema.dated_kind:
-        cols["phys"] = torch.from_numpy(case["phys"].view(np.int64)).to(dev)
-        cols["logical"] = torch.from_numpy(case["logical"].view(np.int32)).to(dev)
-        cols["node"] = torch.from_numpy(case["node"].view(np.int64)).to(dev)
-    if case["tags"] is not None:
-        cols["tags"] = torch.from_numpy(case["tags"]).to(dev)
-    return cols
 
 
 # ---- CPU ------------------------------------------------------------------------------------------
@@ -276,20 +194,8 @@ def test_generated_inputs_cover_the_cases(rsos_hip_lib, w, kind):
 # ---- GPU: the lift ---------------------------------------------------------------------------------
 
 def check_lift(gpu, w, kind, tags, lead, slack):
-    from rsos_hip import lift_records
-    case, want = lift_case(w, kind, tags), lift_want(w, kind, tags)
-    schema = schema_of(w, kind)
-    cols = device_cols(case, schema, gpu, lead, slack)
-    if not slack:  # the first value at heap offset 0, the last record ends at the buffer's end
-        assert cols["values"].numel() == (int(case["offsets"][-1]) + 3) & ~3 and lead == 0
-    fps, bs = lift_records(schema, cols)
-    got, got_bs = fps.cpu().numpy(), bs.cpu().numpy()
-    bad = np.nonzero((got != want).any(axis=1))[0]
-    assert bad.size == 0, (f"rows {bad[:8]} differ (key lengths {[len(case['strs'][i]) for i in bad[:8]]}, "
-                           f"message lengths {[len(case['blobs'][i]) for i in bad[:8]]})")
-    assert got_bs.shape[0] == (case["n"] + 255) // 256
-    for g in range(got_bs.shape[0]):
-        assert int.from_bytes(got_bs[g].tobytes(), "little") == fold(want[256 * g:256 * g + 256]), f"block {g}"
+    RC.check_var_lift(gpu, schema_of(w, kind), lift_case(w, kind, tags), lift_want(w, kind, tags), lead, slack,
+                      tell=("key lengths", "message lengths"))
 
 
 @pytest.mark.gpu
@@ -320,7 +226,7 @@ def test_padding_is_not_hashed(gpu, oracle_lib):
         keys[i, len(s):31] = 0xA5
     assert (keys != case["keys"]).any(axis=1).sum() == sum(1 for s in case["strs"] if len(s) < 31)
     schema = schema_of(32, "dated")
-    fps, _ = lift_records(schema, device_cols(case, schema, gpu, 5, 64, keys=keys))
+    fps, _ = lift_records(schema, RC.device_cols(case, schema, gpu, 5, 64, keys=keys))
     assert np.array_equal(fps.cpu().numpy(), want)
 
 
@@ -346,7 +252,7 @@ def test_dual_lift_equals_the_two_single_lifts(gpu, oracle_lib):
     from rsos_hip import lift_dual, lift_records
     case = lift_case(32, "dated")
     schema = schema_of(32, "dated")
-    cols = device_cols(case, schema, gpu, 5, 64)
+    cols = RC.device_cols(case, schema, gpu, 5, 64)
     fd, bd, fp, bp = lift_dual(schema, cols)
     f1, b1 = lift_records(schema, cols)
     f2, b2 = lift_records(schema_of(32, "projection"), {k: v for k, v in cols.items()
@@ -354,91 +260,12 @@ def test_dual_lift_equals_the_two_single_lifts(gpu, oracle_lib):
     for a, b in ((fd, f1), (bd, b1), (fp, f2), (bp, b2)):
         assert np.array_equal(a.cpu().numpy(), b.cpu().numpy())
     assert np.array_equal(f1.cpu().numpy(), lift_want(32, "dated"))
-    blobs = [canonical("projection", case["strs"][i],
-                       case["heap"][int(case["offsets"][i]):int(case["offsets"][i + 1])], tomb=bool(case["tomb"][i]))
+    blobs = [RC.canonical("str31", "var", "projection", case["strs"][i], case_value(case, i), tomb=bool(case["tomb"][i]))
              for i in range(case["n"])]
     assert np.array_equal(fp.cpu().numpy(), O.lift_encoded(blobs, threads=4))
 
 
 # ---- GPU: the store against a model ----------------------------------------------------------------
-
-class Model:
-    """string -> (record, oracle fingerprint) for a str31 dated var store."""
-
-    W = 32
-
-    def __init__(self):
-        self.rows = {}
-
-    def cols(self, recs):
-        """Host columns of recs = [(key string, (phys, logical, node), tomb, value)], values ragged."""
-        from rsos_hip import pack_str_keys
-        offs = np.zeros(len(recs) + 1, np.uint64)
-        offs[1:] = np.cumsum([len(r[3]) for r in recs])
-        return {"keys": pack_str_keys([r[0] for r in recs], self.W),
-                "phys": np.array([r[1][0] for r in recs], np.uint64),
-                "logical": np.array([r[1][1] for r in recs], np.uint32),
-                "node": np.array([r[1][2] for r in recs], np.uint64),
-                "tags": np.array([r[2] for r in recs], np.uint8),
-                "values": np.frombuffer(b"".join(r[3] for r in recs), np.uint8),
-                "value_offsets": offs}
-
-    def apply(self, recs, ops):
-        """The batch in order (a key met twice keeps its last row), fingerprints from the oracle."""
-        import oracle as O
-        ins = [r for r, op in zip(recs, ops) if op == 0]
-        fps = O.lift_encoded([canonical("dated", r[0], b"" if r[2] else r[3], r[1], bool(r[2])) for r in ins])
-        it = iter(fps)
-        for r, op in zip(recs, ops):
-            if op == 0:
-                self.rows[r[0]] = (r, next(it).tobytes())
-            else:
-                self.rows.pop(r[0], None)
-
-    def check(self, st, absent=()):
-        from rsos_hip.store import KeyRange
-        ks = sorted(self.rows)  # Ord of Vec<u8>
-        n = len(ks)
-        fps = [self.rows[k][1] for k in ks]
-        assert st.size() == n
-        assert agg_int(st.aggregate()) == fold(fps)
-        cuts = sorted({0, n, 1, n // 3, n // 2, n - 1, 255, 256, 257, 511, 512, 513, 700, 768, 1000, 1024, 1025} & set(range(n + 1)))
-        lo = [cuts[i % len(cuts)] for i in range(16)]
-        hi = [cuts[(i * 5 + 3) % len(cuts)] for i in range(16)]
-        for a, l, h in zip(st.aggregates_ranks(lo, hi), lo, hi):
-            assert (a.size, agg_int(a)) == ((h - l, fold(fps[l:h])) if h > l else (0, 0)), (l, h)
-        assert [k for k, _ in st.enumerate()] == ks
-        assert st.fingerprints(0, n).tobytes() == b"".join(fps)
-        import bisect
-        probes = [ks[i] for i in range(0, n, max(n // 24, 1))] + list(absent)
-        for z in probes:
-            assert st.rank(z) == bisect.bisect_left(ks, z), z
-        for r in (0, 1, n // 2, n - 1):
-            assert st.select(r) == ks[r]
-        kinds = ("unbounded", "included", "excluded")
-        for i in range(18):
-            a, b = sorted((probes[(i * 7) % len(probes)], probes[(i * 11 + 3) % len(probes)]))
-            lk, hk = kinds[i % 3], kinds[(i // 3) % 3]
-            rg = KeyRange(None if lk == "unbounded" else a, None if hk == "unbounded" else b, lk, hk)
-            inside = [j for j, k in enumerate(ks)
-                      if (lk == "unbounded" or k > a or (lk == "included" and k == a))
-                      and (hk == "unbounded" or k < b or (hk == "included" and k == b))]
-            got = st.aggregate(rg)
-            assert (got.size, agg_int(got)) == (len(inside), fold(fps[j] for j in inside)), (i, lk, hk, a, b)
-
-
-def ragged_records(rng, keys, long_every=0):
-    out = []
-    for i, k in enumerate(keys):
-        tomb = int(rng.integers(0, 10) == 0)
-        ln = int(rng.integers(0, 200))
-        if long_every and i % long_every == 7:
-            ln = (1500, 3000, 5000, 1024, 960)[(i // long_every) % 5]
-        val = rng.integers(0, 256, ln, dtype=np.uint8).tobytes()
-        stamp = (int(rng.integers(1, 1 << 40)), int(rng.integers(0, 1 << 20)), int(rng.integers(1, 1 << 40)))
-        out.append((k, stamp, tomb, val))
-    return out
-
 
 def string_pool(rng, n):
     """n distinct strings of 0..31 bytes: the order test's prefix families, names, random bytes."""
@@ -470,7 +297,7 @@ def test_store_against_model(gpu, oracle_lib, tier):
     fresh = rest[1000 - len(fixed):]
     absent = fresh[380:400] + [b"a\0\0\0", b"\xff" * 29]
     schema = RecordSchema.dated("str31", "var")
-    st, m = GpuFingerprintStore(schema, host_tier=tier), Model()
+    st, m = GpuFingerprintStore(schema, host_tier=tier), DictModel("str31", "var")
     recs = ragged_records(rng, base, long_every=90)
     st.load_bulk(m.cols(recs))
     m.apply(recs, [0] * len(recs))
@@ -511,15 +338,7 @@ def test_store_against_model(gpu, oracle_lib, tier):
     assert m.rows[again][0][3] == staged[-1][3]
 
     dev = ragged_records(rng, fresh[200:232] + ow[40:72], long_every=16)
-    c = m.cols(dev)
-    heap = np.zeros((c["values"].size + 3) & ~3, np.uint8)
-    heap[:c["values"].size] = c["values"]
-    tc = {"keys": torch.from_numpy(c["keys"].copy()).to(gpu), "phys": torch.from_numpy(c["phys"].view(np.int64)).to(gpu),
-          "logical": torch.from_numpy(c["logical"].view(np.int32)).to(gpu),
-          "node": torch.from_numpy(c["node"].view(np.int64)).to(gpu), "tags": torch.from_numpy(c["tags"]).to(gpu),
-          "values": torch.from_numpy(heap).to(gpu),
-          "value_offsets": torch.from_numpy(c["value_offsets"].astype(np.int64)).to(gpu)}
-    assert st.apply_device(tc, torch.zeros(64, dtype=torch.uint8, device=gpu)) == (32, 32, 0)
+    assert st.apply_device(RC.to_device(m.cols(dev), gpu), torch.zeros(64, dtype=torch.uint8, device=gpu)) == (32, 32, 0)
     m.apply(dev, [0] * 64)
     m.check(st, absent)
 
@@ -557,59 +376,6 @@ def test_store_against_model(gpu, oracle_lib, tier):
 
 # ---- GPU: reconciliation ---------------------------------------------------------------------------
 
-class DictView:
-    """The view oracle/rbsr.py's literal driver asks (size / aggregate / rank / select) over a
-    model's rows: keys in sorted() order of the strings, fingerprints from the oracle."""
-
-    def __init__(self, model):
-        self.ks = sorted(model.rows)
-        self.pre = [0]
-        for k in self.ks:
-            self.pre.append((self.pre[-1] + int.from_bytes(model.rows[k][1], "little")) % MOD)
-
-    def size(self):
-        return len(self.ks)
-
-    def rank(self, k):
-        import bisect
-        return bisect.bisect_left(self.ks, k)
-
-    def select(self, r):
-        return self.ks[r]
-
-    def aggregate(self, start, end):
-        lo = 0 if start is None else self.rank(start)
-        hi = len(self.ks) if end is None else self.rank(end)
-        if hi <= lo:
-            return (0, 0, 0, 0), 0
-        v = (self.pre[hi] - self.pre[lo]) % MOD
-        return tuple((v >> (64 * i)) & (2**64 - 1) for i in range(4)), hi - lo
-
-
-def _outcome(o):
-    return (o.skipped, o.enumerated, o.split, o.children, o.dropped_malformed)
-
-
-def _norm(children):
-    return [c if isinstance(c, tuple) else
-            (c.start, c.end, (tuple(int(x) for x in c.aggregate.fingerprint.limbs), int(c.aggregate.size)))
-            for c in children]
-
-
-def reconcile(a, b, round_fn, init, max_rounds=100):
-    """Ping-pong rounds starting from a's root at b (tests/test_rbsr.py's loop)."""
-    active, sides, log, enums = init(a), [b, a], [], []
-    for k in range(max_rounds):
-        if not active:
-            return log, enums
-        children, en = [], []
-        outcome = round_fn(sides[k % 2], active, children, en)
-        log.append((_norm(children), list(en), outcome))
-        enums.extend(en)
-        active = children
-    raise AssertionError("reconciliation did not terminate")
-
-
 @functools.lru_cache(maxsize=None)
 def recon_sides():
     """Two replicas of 3,000 rows that differ in 7 keys: one changed value, three keys only a
@@ -631,7 +397,7 @@ def recon_sides():
     models = []
     for recs in (a_recs, b_recs):
         recs.sort(key=lambda r: r[0])
-        m = Model()
+        m = DictModel("str31", "var")
         m.apply(recs, [0] * len(recs))
         models.append((recs, m))
     return models, want
@@ -656,10 +422,11 @@ def test_reconciliation_matches_the_literal_driver(gpu, oracle_lib, policy, tier
     a, b = stores
     assert a.size() == b.size() == 3000
     pol, decide = {"fixed16": (R.FixedFanOut(16), OR.fixed_fan_out(16)), "sqrt": (R.SqrtFanOut(), OR.sqrt_fan_out)}[policy]
-    want_log, _ = reconcile(DictView(ma), DictView(mb), lambda v, act, ch, en: OR.protocol_round(v, decide, act, ch, en),
-                            OR.initial_ranges)
-    got_log, ranges = reconcile(a, b, lambda v, act, ch, en: _outcome(R.protocol_round_with_policy(v, pol, act, ch, en)),
-                                R.initial_ranges)
+    want_log = reconcile(DictView(ma), DictView(mb), lambda v, act, ch, en: OR.protocol_round(v, decide, act, ch, en),
+                         OR.initial_ranges, max_rounds=100)[0]
+    got_log, ea, eb = reconcile(a, b, lambda v, act, ch, en: _outcome(R.protocol_round_with_policy(v, pol, act, ch, en)),
+                                R.initial_ranges, max_rounds=100)
+    ranges = ea + eb
     assert len(got_log) == len(want_log) > 2
     for (gc, ge, go), (wc, we, wo) in zip(got_log, want_log):
         assert go == wo and ge == we and gc == wc
@@ -717,7 +484,7 @@ def test_fingerprint_map_with_string_keys(gpu, oracle_lib):
 
     def fp(k):
         v, stamp, tomb = model[k]
-        return O.lift_encoded([canonical("dated", k.encode(), v.encode(), stamp, tomb)])[0].tobytes()
+        return O.lift_encoded([RC.canonical("str31", "var", "dated", k.encode(), v.encode(), stamp, tomb)])[0].tobytes()
     order = sorted(model, key=str.encode)
     assert order == sorted(model)  # code point order is UTF-8 byte order
     agg = fm.aggregate()

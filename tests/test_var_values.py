@@ -2,10 +2,9 @@
 `String` / `Vec<u8>` value whose length differs per record -- the shape of the reference's own
 golden vectors, lift(&50u64, &"Hello") (rsos/src/fingerprint/tests.rs:68-93).
 
-Expected fingerprints come from the oracle alone: every record's canonical bytes are built here
-with oracle/pyref.py's typed model (encode, Str, timestamp, present, TOMBSTONE, entry) and
-hashed by the C oracle (oracle.lift_encoded) -- never by the product's encoder or a second GPU
-kernel.
+Expected fingerprints come from the oracle alone: every record's canonical bytes are built by
+tests/records_common.py with oracle/pyref.py's typed model and hashed by the C oracle
+(oracle.lift_encoded) -- never by the product's encoder or a second GPU kernel.
 """
 import ctypes as C
 import functools
@@ -13,15 +12,14 @@ import functools
 import numpy as np
 import pytest
 
-import pyref as P  # oracle/pyref.py
+import records_common as RC
+from records_common import KINDS, DictModel, agg_int, case_value, fold, prefix_len, ragged_records, to_device
 
-MOD = 1 << 256
 # total message lengths (prefix + value) every shape is run at: block and chunk boundaries on
 # either side, two, three and four chunks (the CV stack merges at 2 and 4), an odd tail
 TOTALS = (63, 64, 65, 127, 128, 129, 1023, 1024, 1025, 2047, 2048, 2049, 3073, 4095, 4096, 4097, 5000)
 SMALL = (0, 1, 2, 3, 4, 5, 7, 8)
 KEYS = ("u32", "u64", "bytes16", "bytes32")
-KINDS = ("plain", "dated", "projection")
 SHAPES = [(k, r) for k in KEYS for r in KINDS] + [("unit", "plain")]
 N_LIFT = 777  # three whole 256-row blocks + a 9-row tail; more than one wave's 256-record range
 
@@ -31,111 +29,22 @@ def schema_of(key, kind):
     return getattr(RecordSchema, kind)(key, "var")
 
 
-def key_enc_len(key):
-    return {"unit": 0, "u32": 4, "u64": 8}.get(key) if not key.startswith("bytes") else 8 + int(key[5:])
-
-
-def prefix_len(key, kind):
-    """P: key encoding, stamp (dated), State variant (dated / projection), the value's u64 length."""
-    return key_enc_len(key) + (20 if kind == "dated" else 0) + (0 if kind == "plain" else 4) + 8
-
-
-def key_model(key, raw: bytes):
-    if key == "unit":
-        return P.Unit()
-    if key == "u32":
-        return P.U32(int.from_bytes(raw, "little"))
-    if key == "u64":
-        return P.U64(int.from_bytes(raw, "little"))
-    return P.Str(raw)  # [u8; L] / Vec<u8>: u64 length, then the bytes
-
-
-def canonical(key, kind, raw_key: bytes, value: bytes, stamp=(0, 0, 0), tomb=False) -> bytes:
-    """rsos::encoding::encode_to_vec(&k) ++ encode_to_vec(&v) by the oracle's typed model."""
-    state = P.TOMBSTONE if tomb else P.present(P.Str(value))
-    if kind == "plain":
-        assert not tomb
-        v = P.Str(value)
-    elif kind == "dated":
-        v = P.entry(P.timestamp(*stamp), state)
-    else:
-        v = state
-    return P.encode(key_model(key, raw_key)) + P.encode(v)
-
-
-def key_width(key):
-    return {"unit": 0, "u32": 4, "u64": 8}.get(key) if not key.startswith("bytes") else int(key[5:])
-
-
-def fold(fps) -> int:
-    return sum(int.from_bytes(bytes(f), "little") for f in fps) % MOD
-
-
-def agg_int(a) -> int:
-    return a.fingerprint.to_int()
-
-
 @functools.lru_cache(maxsize=None)
 def lift_case(key, kind, tags=True):
-    """777 records of one shape: keys, stamps, tags, ragged values packed back to back, and each
-    record's canonical bytes.  Present rows carry every reachable TOTALS length (len = T - P; a
-    total below P cannot occur), the SMALL lengths, and seeded-random lengths in [0, 300) otherwise.
-    With tags every 5th row is a tombstone, one of them over a non-empty span (ignored)."""
-    n, p = N_LIFT, prefix_len(key, kind)
-    rng = np.random.default_rng(sum((key + kind).encode()) * 1000 + p + int(tags))
-    kw = key_width(key)
-    tagged = tags and kind != "plain"
-    tomb = np.array([tagged and i % 5 == 4 for i in range(n)])
-    lens = rng.integers(0, 300, n)
-    special = [t - p for t in TOTALS if t >= p] + list(SMALL)
-    present_rows = [i for i in range(n) if not tomb[i]]
-    slots = rng.choice(present_rows[:-1], len(special), replace=False)
-    for r, ln in zip(slots, special):
-        lens[r] = ln
-    lens[present_rows[-1]] = 37  # the last record is present and not empty: it ends the heap
-    assert present_rows[-1] == n - 1
-    if tagged:
-        lens[tomb] = 0
-        lens[9] = 11  # a tombstone over a non-empty span: the span is ignored
-        assert tomb[9]
-    keys = rng.integers(0, 256, (n, max(kw, 1)), dtype=np.uint8)[:, :kw]
-    phys = rng.integers(0, 1 << 62, n, dtype=np.uint64)
-    logical = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
-    node = rng.integers(0, 1 << 62, n, dtype=np.uint64)
-    values = [rng.integers(0, 256, int(ln), dtype=np.uint8).tobytes() for ln in lens]
-    offsets = np.zeros(n + 1, np.uint64)
-    offsets[1:] = np.cumsum(lens)
-    blobs = [canonical(key, kind, keys[i].tobytes(), values[i], (int(phys[i]), int(logical[i]), int(node[i])),
-                       bool(tomb[i])) for i in range(n)]
-    return {"n": n, "p": p, "keys": keys, "phys": phys, "logical": logical, "node": node,
-            "tags": tomb.astype(np.uint8) if tagged else None, "lens": lens, "heap": b"".join(values),
-            "offsets": offsets, "blobs": blobs, "tomb": tomb}
+    """777 records of one shape (records_common.build_lift_case).  Present rows carry every
+    reachable TOTALS length (len = T - P; a total below P cannot occur) and the SMALL lengths; the
+    last record is present."""
+    p = prefix_len(key, kind)
+    case = RC.build_lift_case(key, "var", kind, tags, N_LIFT, sum((key + kind).encode()) * 1000 + p + int(tags),
+                              totals=TOTALS, small=SMALL)
+    assert not case["tomb"][N_LIFT - 1]
+    return case
 
 
 @functools.lru_cache(maxsize=None)
 def lift_want(key, kind, tags=True):
     import oracle as O
     return O.lift_encoded(lift_case(key, kind, tags)["blobs"], threads=4)
-
-
-def device_cols(case, schema, dev, lead=0, slack=0):
-    """The case as device columns; the heap is `lead` bytes of filler, the values, `slack` bytes
-    of filler, then filler up to a multiple of 4 (0xA5: a byte read past a value would show)."""
-    import torch
-    used = lead + len(case["heap"]) + slack
-    heap = np.full((used + 3) & ~3, 0xA5, np.uint8)
-    heap[lead:lead + len(case["heap"])] = np.frombuffer(case["heap"], np.uint8)
-    cols = {"values": torch.from_numpy(heap).to(dev),
-            "value_offsets": torch.from_numpy((case["offsets"] + np.uint64(lead)).astype(np.int64)).to(dev)}
-    if schema.key_row:
-        cols["keys"] = torch.from_numpy(np.ascontiguousarray(case["keys"])).to(dev)
-    if schema.dated_kind:
-        cols["phys"] = torch.from_numpy(case["phys"].view(np.int64)).to(dev)
-        cols["logical"] = torch.from_numpy(case["logical"].view(np.int32)).to(dev)
-        cols["node"] = torch.from_numpy(case["node"].view(np.int64)).to(dev)
-    if case["tags"] is not None:
-        cols["tags"] = torch.from_numpy(case["tags"]).to(dev)
-    return cols
 
 
 # ---- CPU ------------------------------------------------------------------------------------------
@@ -209,19 +118,7 @@ def test_fmap_rows_accept_any_length(rsos_hip_lib):
 # ---- GPU: the lift ---------------------------------------------------------------------------------
 
 def check_lift(gpu, key, kind, tags, lead, slack):
-    from rsos_hip import lift_records
-    case, want = lift_case(key, kind, tags), lift_want(key, kind, tags)
-    schema = schema_of(key, kind)
-    cols = device_cols(case, schema, gpu, lead, slack)
-    if not slack:  # the last record ends at the buffer's end
-        assert cols["values"].numel() == (int(case["offsets"][-1]) + 3) & ~3 and lead == 0
-    fps, bs = lift_records(schema, cols)
-    got, got_bs = fps.cpu().numpy(), bs.cpu().numpy()
-    bad = np.nonzero((got != want).any(axis=1))[0]
-    assert bad.size == 0, f"rows {bad[:8]} differ (message lengths {[len(case['blobs'][i]) for i in bad[:8]]})"
-    assert got_bs.shape[0] == (case["n"] + 255) // 256
-    for g in range(got_bs.shape[0]):
-        assert int.from_bytes(got_bs[g].tobytes(), "little") == fold(want[256 * g:256 * g + 256]), f"block {g}"
+    RC.check_var_lift(gpu, schema_of(key, kind), lift_case(key, kind, tags), lift_want(key, kind, tags), lead, slack)
 
 
 @pytest.mark.gpu
@@ -273,7 +170,7 @@ def test_dual_lift_equals_the_two_single_lifts(gpu, oracle_lib):
     from rsos_hip import lift_dual, lift_records
     case = lift_case("bytes16", "dated")
     schema = schema_of("bytes16", "dated")
-    cols = device_cols(case, schema, gpu, 5, 64)
+    cols = RC.device_cols(case, schema, gpu, 5, 64)
     fd, bd, fp, bp = lift_dual(schema, cols)
     f1, b1 = lift_records(schema, cols)
     f2, b2 = lift_records(schema_of("bytes16", "projection"), {k: v for k, v in cols.items()
@@ -283,78 +180,12 @@ def test_dual_lift_equals_the_two_single_lifts(gpu, oracle_lib):
     assert np.array_equal(f1.cpu().numpy(), lift_want("bytes16", "dated"))
     # the projection of the same rows, from the oracle
     import oracle as O
-    blobs = [canonical("bytes16", "projection", case["keys"][i].tobytes(),
-                       case["heap"][int(case["offsets"][i]):int(case["offsets"][i + 1])], tomb=bool(case["tomb"][i]))
-             for i in range(case["n"])]
+    blobs = [RC.canonical("bytes16", "var", "projection", case["keys"][i].tobytes(), case_value(case, i),
+                          tomb=bool(case["tomb"][i])) for i in range(case["n"])]
     assert np.array_equal(fp.cpu().numpy(), O.lift_encoded(blobs, threads=4))
 
 
 # ---- GPU: the store against a model ----------------------------------------------------------------
-
-class Model:
-    """key -> (stamp, tomb, value, oracle fingerprint) for a bytes16 / u64 dated var store."""
-
-    def __init__(self, key):
-        self.key, self.rows = key, {}
-
-    def cols(self, recs):
-        """Host columns of recs = [(key bytes, (phys, logical, node), tomb, value)], values ragged."""
-        kw = key_width(self.key)
-        keys = np.frombuffer(b"".join(r[0] for r in recs), np.uint8).reshape(len(recs), kw)
-        offs = np.zeros(len(recs) + 1, np.uint64)
-        offs[1:] = np.cumsum([len(r[3]) for r in recs])
-        return {"keys": keys.view(np.uint64).reshape(-1) if self.key == "u64" else keys,
-                "phys": np.array([r[1][0] for r in recs], np.uint64),
-                "logical": np.array([r[1][1] for r in recs], np.uint32),
-                "node": np.array([r[1][2] for r in recs], np.uint64),
-                "tags": np.array([r[2] for r in recs], np.uint8),
-                "values": np.frombuffer(b"".join(r[3] for r in recs), np.uint8),
-                "value_offsets": offs}
-
-    def apply(self, recs, ops):
-        """The batch in order (a key met twice keeps its last row), fingerprints from the oracle."""
-        import oracle as O
-        ins = [r for r, op in zip(recs, ops) if op == 0]
-        fps = O.lift_encoded([canonical(self.key, "dated", r[0], b"" if r[2] else r[3], r[1], bool(r[2])) for r in ins])
-        it = iter(fps)
-        for r, op in zip(recs, ops):
-            if op == 0:
-                self.rows[r[0]] = (r, next(it).tobytes())
-            else:
-                self.rows.pop(r[0], None)
-
-    def order(self):
-        ks = list(self.rows)
-        return sorted(ks, key=(lambda k: int.from_bytes(k, "little")) if self.key == "u64" else None)
-
-    def check(self, st):
-        ks = self.order()
-        n = len(ks)
-        fps = [self.rows[k][1] for k in ks]
-        assert st.size() == n
-        assert agg_int(st.aggregate()) == fold(fps)
-        cuts = sorted({0, n, 1, n // 3, n // 2, n - 1, 255, 256, 257, 511, 512, 513, 700, 768, 1000, 1024, 1025} & set(range(n + 1)))
-        lo = [cuts[i % len(cuts)] for i in range(16)]
-        hi = [cuts[(i * 5 + 3) % len(cuts)] for i in range(16)]
-        for a, l, h in zip(st.aggregates_ranks(lo, hi), lo, hi):
-            assert (a.size, agg_int(a)) == ((h - l, fold(fps[l:h])) if h > l else (0, 0)), (l, h)
-        got_keys = [k for k, _ in st.enumerate()]
-        assert got_keys == [int.from_bytes(k, "little") if self.key == "u64" else k for k in ks]
-        assert st.fingerprints(0, n).tobytes() == b"".join(fps)
-
-
-def ragged_records(rng, keys, long_every=0):
-    out = []
-    for i, k in enumerate(keys):
-        tomb = int(rng.integers(0, 10) == 0)
-        ln = int(rng.integers(0, 200))
-        if long_every and i % long_every == 7:
-            ln = (1500, 3000, 5000, 1024, 960)[(i // long_every) % 5]
-        val = rng.integers(0, 256, ln, dtype=np.uint8).tobytes()
-        stamp = (int(rng.integers(1, 1 << 40)), int(rng.integers(0, 1 << 20)), int(rng.integers(1, 1 << 40)))
-        out.append((k, stamp, tomb, val))
-    return out
-
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("tier", [False, True], ids=["device", "tier"])
@@ -370,7 +201,7 @@ def test_store_against_model(gpu, oracle_lib, tier):
     rng.shuffle(pool)
     base, fresh = sorted(pool[:1000]), pool[1000:]
     schema = RecordSchema.dated("bytes16", "var")
-    st, m = GpuFingerprintStore(schema, host_tier=tier), Model("bytes16")
+    st, m = GpuFingerprintStore(schema, host_tier=tier), DictModel("bytes16", "var")
     # the batches go the large-batch way, whatever their size
     recs = ragged_records(rng, base, long_every=90)
     st.load_bulk(m.cols(recs))
@@ -413,15 +244,7 @@ def test_store_against_model(gpu, oracle_lib, tier):
     assert m.rows[again][0][3] == staged[-1][3]
 
     dev = ragged_records(rng, fresh[200:232] + ow[40:72], long_every=16)
-    c = m.cols(dev)
-    heap = np.zeros((c["values"].size + 3) & ~3, np.uint8)
-    heap[:c["values"].size] = c["values"]
-    tc = {"keys": torch.from_numpy(c["keys"].copy()).to(gpu), "phys": torch.from_numpy(c["phys"].view(np.int64)).to(gpu),
-          "logical": torch.from_numpy(c["logical"].view(np.int32)).to(gpu),
-          "node": torch.from_numpy(c["node"].view(np.int64)).to(gpu), "tags": torch.from_numpy(c["tags"]).to(gpu),
-          "values": torch.from_numpy(heap).to(gpu),
-          "value_offsets": torch.from_numpy(c["value_offsets"].astype(np.int64)).to(gpu)}
-    new, over, dele = st.apply_device(tc, torch.zeros(64, dtype=torch.uint8, device=gpu))
+    new, over, dele = st.apply_device(to_device(m.cols(dev), gpu), torch.zeros(64, dtype=torch.uint8, device=gpu))
     assert (new, over, dele) == (32, 32, 0)
     m.apply(dev, [0] * 64)
     m.check(st)
@@ -432,14 +255,7 @@ def test_store_against_model(gpu, oracle_lib, tier):
     if sum(len(r[3]) for r in many[0]) % 4 == 0:
         many[0][0] = (many[0][0][0], many[0][0][1], many[0][0][2], many[0][0][3] + b"x")
     mops = [[0] * 48, [1] * 16 + [0] * 16]
-    tcs = []
-    for recs in many:
-        c = m.cols(recs)
-        tcs.append({"keys": torch.from_numpy(c["keys"].copy()).to(gpu), "phys": torch.from_numpy(c["phys"].view(np.int64)).to(gpu),
-                    "logical": torch.from_numpy(c["logical"].view(np.int32)).to(gpu),
-                    "node": torch.from_numpy(c["node"].view(np.int64)).to(gpu), "tags": torch.from_numpy(c["tags"]).to(gpu),
-                    "values": torch.from_numpy(c["values"].copy()).to(gpu),
-                    "value_offsets": torch.from_numpy(c["value_offsets"].astype(np.int64)).to(gpu)})
+    tcs = [to_device(m.cols(recs), gpu, pad_heap=False) for recs in many]
     assert tcs[0]["values"].numel() % 4 != 0
     got = st.apply_device_many(tcs, [torch.from_numpy(np.array(o, np.uint8)).to(gpu) for o in mops])
     assert got == [(32, 16, 0), (16, 0, 16)]
@@ -495,7 +311,7 @@ def test_reconciliation_finds_the_differing_keys(gpu, oracle_lib, tier):
     schema = RecordSchema.dated("u64", "var")
     sides = []
     for recs in (a_recs, b_recs):
-        st, m = GpuFingerprintStore(schema, host_tier=tier), Model("u64")
+        st, m = GpuFingerprintStore(schema, host_tier=tier), DictModel("u64", "var")
         st.load_bulk(m.cols(recs))
         m.apply(recs, [0] * len(recs))
         sides.append((st, m))
@@ -545,7 +361,7 @@ def test_fingerprint_map_with_string_values(gpu, oracle_lib):
     del model[25]
 
     def want():
-        return fold(O.lift_encoded([canonical("u64", "plain", k.to_bytes(8, "little"), v) for k, v in sorted(model.items())]))
+        return fold(O.lift_encoded([RC.canonical("u64", "var", "plain", k.to_bytes(8, "little"), v) for k, v in sorted(model.items())]))
     agg = fm.aggregate()
     assert (agg.size, agg_int(agg)) == (len(model), want())
     assert fm.insert(9, b"short now") == bytes(range(200)) * 9
