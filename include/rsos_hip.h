@@ -373,6 +373,17 @@ typedef struct rh_round_outcome { /* RoundOutcome (protocol.rs:135-142)         
 } rh_round_outcome;
 int rh_store_protocol_round(rh_store *store, int policy, uint64_t fan_out, const rh_segments *active,
                             rh_segments *children, rh_segments *enumerations, rh_round_outcome *outcome);
+/* The same round under the third shipped policy, EnumerateBelowThreshold(threshold, fan_out)
+ * (rbsr/src/policy/enumerate_below_threshold.rs:141-153; Algorithm 1 as written): SKIP when the two
+ * aggregates agree, else IDLIST when the local span <= threshold, else SPLIT with stride
+ * ceil(span / fan_out).  threshold 0 is raised to 1 and fan_out < 2 to 2 (:117-122); PAPER is
+ * (32, 16).  It replaces the shared cutoffs: a span of 0 or 1 against a larger remote side is an
+ * IDLIST (bounced back as one child with the ZERO aggregate), not a stride-1 split.  Argument
+ * checks, output ownership, the one-snapshot rule and the host tier's routing are those of
+ * rh_store_protocol_round, which keeps refusing any policy but its two.                         */
+int rh_store_protocol_round_threshold(rh_store *store, uint64_t threshold, uint64_t fan_out,
+                                      const rh_segments *active, rh_segments *children,
+                                      rh_segments *enumerations, rh_round_outcome *outcome);
 
 /* ---- Enumerate, batched ---------------------------------------------------------------------
  * Rsos::enumerate (rsos/src/rsos_trait.rs:73-83) for every IDLIST range of a round at once: the
@@ -401,6 +412,12 @@ int rh_store_protocol_round(rh_store *store, int policy, uint64_t fan_out, const
  * struct itself.  On rh_sstore the output is the sharded store's own buffer, never a shard's.
  * n = 0 answers rows = 0 with no device call; an empty store answers all zeros; a broken sharded map
  * is RH_ERR_STATE.
+ * A handful of ranges: on the device, at most 16 ranges over rows of at most 32 bytes are answered
+ * by one launch (k_enum_tiny) whenever their rows number at most 512 in all (16 ranges of
+ * EnumerateBelowThreshold's t = 32); a larger total is answered by the general path in one more trip,
+ * with the same bytes.  RSOS_HIP_ENUM_FUSED=0 in the environment when the store is created selects the
+ * general path always.  rh_store_enumerate_stats counts the device calls each way (host-tier answers
+ * and empty stores are neither).
  * Host tier: the same answers; with a fresh tier and ranges->n <= round_max (whenever
  * rh_store_resolve_segments would be) the call is answered on the host, no device round trip.
  * Sharded map: a range inside one shard is that shard's range, a range that straddles splitters
@@ -417,6 +434,7 @@ typedef struct rh_enumerated {
 } rh_enumerated;
 int rh_store_enumerate_segments(rh_store *store, const rh_segments *ranges, uint64_t max_rows,
                                 rh_enumerated *out);
+int rh_store_enumerate_stats(rh_store *store, uint64_t *one_launch, uint64_t *general);
 
 /* Host tier (the diff path is latency-bound).  enable = 1 keeps, next to the
  * HBM-resident store, a host copy of the keys in rank order and the exclusive prefix sums of the
@@ -839,6 +857,11 @@ int rh_sstore_split_segments(rh_sstore *store, size_t m, const uint64_t *select_
                              const uint64_t *lo, const uint64_t *hi, rh_aggregate *out);
 int rh_sstore_protocol_round(rh_sstore *store, int policy, uint64_t fan_out, const rh_segments *active,
                              rh_segments *children, rh_segments *enumerations, rh_round_outcome *outcome);
+/* rh_store_protocol_round_threshold over the shards (enumerate_below_threshold.rs:141-153): the
+ * shards' own rounds and the segments straddling a splitter decide by the same threshold         */
+int rh_sstore_protocol_round_threshold(rh_sstore *store, uint64_t threshold, uint64_t fan_out,
+                                       const rh_segments *active, rh_segments *children,
+                                       rh_segments *enumerations, rh_round_outcome *outcome);
 /* rh_store_enumerate_segments over the shards (its contract above): a straddling range's pieces
  * in shard order, global first ranks, the output in the sharded store's own buffer              */
 int rh_sstore_enumerate_segments(rh_sstore *store, const rh_segments *ranges, uint64_t max_rows,
@@ -855,11 +878,12 @@ int rh_sstore_compact(rh_sstore *store);
  * run after a large batch: the batch still succeeds, the tier goes stale), "small_batch.merge"
  * (the next small batch's delta merge is reported failed when the store is next entered: that call
  * and every later one return RH_ERR_HIP naming it, until a load replaces the contents),
- * "sstore.apply_last_shard" (a sharded apply's last shard).  Three points instead make the next
+ * "sstore.apply_last_shard" (a sharded apply's last shard).  Four points instead make the next
  * launch waited for through a sequence word find that word already holding the number it will
  * store, as a reused buffer may: "round.stale_seq" (a one-launch device round), "query.stale_seq"
- * (a one-launch device rank / select / aggregate), "small_batch.stale_seq" (a small batch); the
- * answer must not change.  For tests only.                                                   */
+ * (a one-launch device rank / select / aggregate), "enum.stale_seq" (a one-launch device
+ * enumerate), "small_batch.stale_seq" (a small batch); the answer must not change.  For tests
+ * only.                                                                                      */
 int rh_debug_fail_point(const char *name);
 
 /* ---- measurement -----------------------------------------------------------------------

@@ -16,9 +16,10 @@ int check_schema_arg(const rh_schema *s);         // check_schema: RH_ERR_ARG na
 // row; RH_OK for every other key kind.  Checked here for the whole batch before any shard changes
 int check_str_rows(const rh_schema &s, const void *keys, size_t n);
 // rh_store_protocol_round in two halves (rsos_hip_abi.hip round_entry): a device round issued
-// (*pending: the store stays locked) and completed later on the same thread
+// (*pending: the store stays locked) and completed later on the same thread.  threshold != 0: the
+// round of rh_store_protocol_round_threshold (policy is then RH_POLICY_FIXED_FAN_OUT)
 int store_round_issue(rh_store *s, int policy, uint64_t fan_out, const rh_segments *active, rh_segments *children,
-                      rh_segments *enumerations, rh_round_outcome *outcome, bool *pending);
+                      rh_segments *enumerations, rh_round_outcome *outcome, bool *pending, uint64_t threshold = 0);
 int store_round_complete(rh_store *s, rh_segments *children, rh_segments *enumerations, rh_round_outcome *outcome);
 // what both enumerate entry points check before any device call: NULL arguments, the bound kinds and
 // key arrays (rh_store_resolve_segments' rule), max_rows (0 becomes 2^22, more is RH_ERR_ARG); *out zeroed

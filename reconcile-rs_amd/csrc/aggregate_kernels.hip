@@ -303,13 +303,13 @@ __global__ __launch_bounds__(256) void k_range_query_wave(const uint8_t *fps, ui
 // hdr gets the RoundOutcome counts (protocol.rs:135-142) -- skipped, enumerated, split,
 // children, dropped
 __global__ __launch_bounds__(256) void k_round_plan(RoundSegs g, const uint64_t *remote, uint64_t r, uint64_t n,
-                                                    int sqrt_policy, uint64_t b, uint64_t *hdr) {
+                                                    int sqrt_policy, uint64_t b, uint64_t *hdr, uint64_t thr) {
     __shared__ unsigned long long cnt[5];
     if (threadIdx.x < 5) cnt[threadIdx.x] = 0;
     __syncthreads();
     const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j < r) {
-        const RoundSeg d = round_decide(g.lo[j], g.hi[j], g.loc + 5 * j, remote + 5 * j, n, sqrt_policy, b);
+        const RoundSeg d = round_decide(g.lo[j], g.hi[j], g.loc + 5 * j, remote + 5 * j, n, sqrt_policy, b, thr);
         g.kind[j] = (uint8_t)d.kind;
         g.stride[j] = d.stride;
         g.si[j] = d.si;
@@ -327,13 +327,13 @@ __global__ __launch_bounds__(256) void k_round_plan(RoundSegs g, const uint64_t 
 // were six): decisions and per-256-segment counts; one workgroup scans the parts and writes the
 // header; each segment's child / enumeration offsets ---------------------------------------------
 __global__ __launch_bounds__(256) void k_round_plan_part(RoundSegs g, const uint64_t *remote, uint64_t r, uint64_t n,
-                                                         int sqrt_policy, uint64_t b, uint64_t *part) {
+                                                         int sqrt_policy, uint64_t b, uint64_t *part, uint64_t thr) {
     __shared__ unsigned long long cnt[5];  // skipped, enumerated (= enumerations), split, children, dropped
     if (threadIdx.x < 5) cnt[threadIdx.x] = 0;
     __syncthreads();
     const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j < r) {
-        const RoundSeg d = round_decide(g.lo[j], g.hi[j], g.loc + 5 * j, remote + 5 * j, n, sqrt_policy, b);
+        const RoundSeg d = round_decide(g.lo[j], g.hi[j], g.loc + 5 * j, remote + 5 * j, n, sqrt_policy, b, thr);
         g.kind[j] = (uint8_t)d.kind;
         g.stride[j] = d.stride;
         g.si[j] = d.si;
@@ -670,7 +670,7 @@ __global__ __launch_bounds__(256) void k_round_bounds(const uint32_t *rank, Roun
 
 __global__ __launch_bounds__(1024) void k_round_small(const uint32_t *rank, RoundIn in, RoundSegs g, uint64_t r,
                                                       uint64_t n, int sqrt_policy, uint64_t b, uint64_t cap,
-                                                      uint32_t kl, uint8_t *out) {
+                                                      uint32_t kl, uint8_t *out, uint64_t thr) {
     __shared__ uint64_t wsum[2][16], tot[2];
     __shared__ unsigned long long cnt[5];
     const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
@@ -690,7 +690,7 @@ __global__ __launch_bounds__(1024) void k_round_small(const uint32_t *rank, Roun
     __syncthreads();
     RoundSeg d{3, 0, 0, 0, 0, 0};
     if (mine) {
-        d = round_decide(g.lo[t], g.hi[t], g.loc + 5 * t, in.remote + 5 * t, n, sqrt_policy, b);
+        d = round_decide(g.lo[t], g.hi[t], g.loc + 5 * t, in.remote + 5 * t, n, sqrt_policy, b, thr);
         g.kind[t] = (uint8_t)d.kind;
         g.stride[t] = d.stride;
         g.si[t] = d.si;
@@ -728,7 +728,7 @@ __global__ __launch_bounds__(1024) void k_round_small(const uint32_t *rank, Roun
 __global__ __launch_bounds__(1024) void k_round_small_view(const uint32_t *rank_b, const uint32_t *rank_j, RoundIn in,
                                                            RoundRun R, RoundSegs g, uint64_t *place, uint64_t r,
                                                            uint64_t n, int sqrt_policy, uint64_t b, uint64_t cap,
-                                                           uint32_t kl, uint8_t *out) {
+                                                           uint32_t kl, uint8_t *out, uint64_t thr) {
     __shared__ uint64_t wsum[2][16], tot[2];
     __shared__ unsigned long long cnt[5];
     const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
@@ -739,7 +739,7 @@ __global__ __launch_bounds__(1024) void k_round_small_view(const uint32_t *rank_
     __syncthreads();
     RoundSeg d{3, 0, 0, 0, 0, 0};
     if (mine) {
-        d = round_decide(g.lo[t], g.hi[t], g.loc + 5 * t, in.remote + 5 * t, n, sqrt_policy, b);
+        d = round_decide(g.lo[t], g.hi[t], g.loc + 5 * t, in.remote + 5 * t, n, sqrt_policy, b, thr);
         g.kind[t] = (uint8_t)d.kind;
         g.stride[t] = d.stride;
         g.si[t] = d.si;
@@ -773,7 +773,7 @@ __global__ __launch_bounds__(1024) void k_round_small_view(const uint32_t *rank_
     }
 }
 __global__ __launch_bounds__(1024) void k_round_plan_scan(RoundIn in, RoundSegs g, uint64_t r, uint64_t n,
-                                                          int sqrt_policy, uint64_t b, uint8_t *out) {
+                                                          int sqrt_policy, uint64_t b, uint8_t *out, uint64_t thr) {
     __shared__ uint64_t wsum[2][16], tot[2];
     __shared__ unsigned long long cnt[5];
     const uint32_t t = threadIdx.x;
@@ -782,7 +782,7 @@ __global__ __launch_bounds__(1024) void k_round_plan_scan(RoundIn in, RoundSegs 
     const bool mine = t < r;
     RoundSeg d{3, 0, 0, 0, 0, 0};
     if (mine) {
-        d = round_decide(g.lo[t], g.hi[t], g.loc + 5 * t, in.remote + 5 * t, n, sqrt_policy, b);
+        d = round_decide(g.lo[t], g.hi[t], g.loc + 5 * t, in.remote + 5 * t, n, sqrt_policy, b, thr);
         g.kind[t] = (uint8_t)d.kind;
         g.stride[t] = d.stride;
         g.si[t] = d.si;
@@ -1076,20 +1076,20 @@ hipError_t launch_range_query(const uint8_t *fps, const uint8_t *bsums, const ui
 }
 
 hipError_t launch_round_plan3(const RoundSegs &g, const uint64_t *remote, uint64_t r, uint64_t n, int sqrt_policy,
-                              uint64_t b, uint64_t *part, uint64_t *hdr, hipStream_t st) {
+                              uint64_t b, uint64_t *part, uint64_t *hdr, hipStream_t st, uint64_t thr) {
     if (r == 0) return hipSuccess;
     const uint64_t np = (r + 255) / 256;
-    hipLaunchKernelGGL(k_round_plan_part, dim3((uint32_t)np), dim3(256), 0, st, g, remote, r, n, sqrt_policy, b, part);
+    hipLaunchKernelGGL(k_round_plan_part, dim3((uint32_t)np), dim3(256), 0, st, g, remote, r, n, sqrt_policy, b, part, thr);
     hipLaunchKernelGGL(k_round_plan_scan_parts, dim3(1), dim3(1024), 0, st, part, np, hdr);
     hipLaunchKernelGGL(k_round_plan_apply, dim3((uint32_t)np), dim3(256), 0, st, g, r, (const uint64_t *)part);
     return hipGetLastError();
 }
 
 hipError_t launch_round_plan(const RoundSegs &g, const uint64_t *remote, uint64_t r, uint64_t n, int sqrt_policy,
-                             uint64_t b, uint64_t *hdr, hipStream_t st) {
+                             uint64_t b, uint64_t *hdr, hipStream_t st, uint64_t thr) {
     if (r == 0) return hipSuccess;
     hipLaunchKernelGGL(k_round_plan, dim3((uint32_t)((r + 255) / 256)), dim3(256), 0, st, g, remote, r, n,
-                       sqrt_policy, b, hdr);
+                       sqrt_policy, b, hdr, thr);
     return hipGetLastError();
 }
 
@@ -1212,27 +1212,28 @@ uint64_t round_tiny_max() { return ROUND_TINY; }
 uint64_t round_small_max() { return ROUND_SMALL; }
 
 hipError_t launch_round_plan_scan(const RoundIn &in, const RoundSegs &g, uint64_t r, uint64_t n, int sqrt_policy,
-                                  uint64_t b, uint8_t *out, hipStream_t st) {
+                                  uint64_t b, uint8_t *out, hipStream_t st, uint64_t thr) {
     if (r == 0 || r > ROUND_SMALL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_round_plan_scan, dim3(1), dim3(ROUND_SMALL), 0, st, in, g, r, n, sqrt_policy, b, out);
+    hipLaunchKernelGGL(k_round_plan_scan, dim3(1), dim3(ROUND_SMALL), 0, st, in, g, r, n, sqrt_policy, b, out, thr);
     return hipGetLastError();
 }
 
 hipError_t launch_round_small(const uint32_t *rank, const RoundIn &in, const RoundSegs &g, uint64_t r, uint64_t n,
-                              int sqrt_policy, uint64_t b, uint64_t cap, uint32_t kl, uint8_t *out, hipStream_t st) {
+                              int sqrt_policy, uint64_t b, uint64_t cap, uint32_t kl, uint8_t *out, hipStream_t st,
+                              uint64_t thr) {
     if (r == 0 || r > ROUND_TINY) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_round_small, dim3(1), dim3(ROUND_SMALL), 0, st, rank, in, g, r, n, sqrt_policy, b, cap, kl,
-                       out);
+                       out, thr);
     return hipGetLastError();
 }
 
 hipError_t launch_round_small_view(const uint32_t *rank_b, const uint32_t *rank_j, const RoundIn &in,
                                    const RoundRun &run, const RoundSegs &g, uint64_t *place, uint64_t r, uint64_t n,
                                    int sqrt_policy, uint64_t b, uint64_t cap, uint32_t kl, uint8_t *out,
-                                   hipStream_t st) {
+                                   hipStream_t st, uint64_t thr) {
     if (r == 0 || r > ROUND_TINY) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_round_small_view, dim3(1), dim3(ROUND_SMALL), 0, st, rank_b, rank_j, in, run, g, place, r, n,
-                       sqrt_policy, b, cap, kl, out);
+                       sqrt_policy, b, cap, kl, out, thr);
     return hipGetLastError();
 }
 

@@ -571,8 +571,9 @@ struct HostTier {
     std::vector<uint64_t> bb_, bj_, cut_r_, cut_b_, cut_j_;
     std::vector<const uint8_t *> cut_k_;
     std::vector<Cur> cuts_;
-    void round(int sqrt_policy, uint64_t b, const rh_segments &in, std::vector<uint8_t> &out, uint64_t hdr[5]) {
-        if (batch && keys && in.n > 1) return round_batched(sqrt_policy, b, in, out, hdr);
+    void round(int sqrt_policy, uint64_t b, const rh_segments &in, std::vector<uint8_t> &out, uint64_t hdr[5],
+               uint64_t thr = 0) {
+        if (batch && keys && in.n > 1) return round_batched(sqrt_policy, b, in, out, hdr, thr);
         const size_t r = in.n;
         const uint8_t *sk = in.start_kinds, *ek = in.end_kinds;
         const uint8_t *skeys = static_cast<const uint8_t *>(in.start_keys);
@@ -583,7 +584,7 @@ struct HostTier {
             Seg &g = segs[j];
             g = Seg{3, 0, 0, 0, sk[j] ? lt(skeys + j * kl) : begin(), ek[j] ? lt(ekeys + j * kl) : end(), {}};
             agg(g.cs, g.ce, &g.loc);
-            const SegDecision d = decide_segment(g.cs.r, g.ce.r, g.loc, in.aggregates[j], sqrt_policy, b);
+            const SegDecision d = decide_segment(g.cs.r, g.ce.r, g.loc, in.aggregates[j], sqrt_policy, b, thr);
             g.kind = d.kind, g.stride = d.stride, g.children = d.children, g.enums = d.enums;
             cnt[g.kind == 3 ? 4 : g.kind]++;
             nc += g.children;
@@ -639,7 +640,8 @@ struct HostTier {
     // batch of searches (view_lt_batch, view_at_batch), the prefix lines requested before they are
     // read; a tree adds its own (cached) search per bound and keeps select key by key.  The same
     // answers as the key-by-key path (tests/host_tier_check.cpp compares the two).
-    void round_batched(int sqrt_policy, uint64_t b, const rh_segments &in, std::vector<uint8_t> &out, uint64_t hdr[5]) {
+    void round_batched(int sqrt_policy, uint64_t b, const rh_segments &in, std::vector<uint8_t> &out, uint64_t hdr[5],
+                       uint64_t thr = 0) {
         const size_t r = in.n;
         const uint8_t *sk = in.start_kinds, *ek = in.end_kinds;
         const uint8_t *skeys = static_cast<const uint8_t *>(in.start_keys);
@@ -673,7 +675,7 @@ struct HostTier {
             if (ek[j]) ce.b = bb_[qi], ce.j = bj_[qi], bound_place(ce), qi++;
             g = Seg{3, 0, 0, 0, cs, ce, {}};
             agg(g.cs, g.ce, &g.loc);
-            const SegDecision d = decide_segment(g.cs.r, g.ce.r, g.loc, in.aggregates[j], sqrt_policy, b);
+            const SegDecision d = decide_segment(g.cs.r, g.ce.r, g.loc, in.aggregates[j], sqrt_policy, b, thr);
             g.kind = d.kind, g.stride = d.stride, g.children = d.children, g.enums = d.enums;
             cnt[g.kind == 3 ? 4 : g.kind]++;
             nc += g.children;

@@ -129,7 +129,7 @@ hipError_t launch_round_bounds_view(const uint32_t *rank_b, const uint32_t *rank
 hipError_t launch_round_small_view(const uint32_t *rank_b, const uint32_t *rank_j, const RoundIn &in,
                                    const RoundRun &run, const RoundSegs &g, uint64_t *place, uint64_t r, uint64_t n,
                                    int sqrt_policy, uint64_t b, uint64_t cap, uint32_t kl, uint8_t *out,
-                                   hipStream_t st);
+                                   hipStream_t st, uint64_t thr = 0);
 // the two-call path's step 1 over the view: bound keys interleaved (row 2 j start, 2 j + 1 end)
 hipError_t launch_resolve_view(const uint32_t *rank_b, const uint32_t *rank_j, const uint8_t *sk, const uint8_t *ek,
                                const RoundIn &in, const RoundRun &run, uint64_t r, uint64_t *lo, uint64_t *hi,
@@ -146,13 +146,14 @@ hipError_t launch_round_emit_view(const uint64_t *hdr, uint64_t cap, uint64_t r,
                                   hipStream_t st);
 // large rounds: decisions (g.lo / g.hi / g.loc filled) -> hdr (zeroed by the caller) gets the
 // outcome counts; after the offsets are scanned, children and enumerations into `out`
-// (round_layout(hdr children, hdr enumerated, kl)), nothing when the children outnumber cap
+// (round_layout(hdr children, hdr enumerated, kl)), nothing when the children outnumber cap.
+// thr (every planner below): EnumerateBelowThreshold's t, or 0 for the shared cutoffs (round_decide)
 // the plan, the child / enumeration offsets and the header in three launches (part: 5 u64 per 256
 // segments)
 hipError_t launch_round_plan3(const RoundSegs &g, const uint64_t *remote, uint64_t r, uint64_t n, int sqrt_policy,
-                              uint64_t b, uint64_t *part, uint64_t *hdr, hipStream_t st);
+                              uint64_t b, uint64_t *part, uint64_t *hdr, hipStream_t st, uint64_t thr = 0);
 hipError_t launch_round_plan(const RoundSegs &g, const uint64_t *remote, uint64_t r, uint64_t n, int sqrt_policy,
-                             uint64_t b, uint64_t *hdr, hipStream_t st);
+                             uint64_t b, uint64_t *hdr, hipStream_t st, uint64_t thr = 0);
 hipError_t launch_round_emit(const uint64_t *hdr, uint64_t cap, uint64_t r, uint32_t kl, const RoundIn &in,
                              const RoundSegs &g, uint8_t *out, hipStream_t st);
 // the round (round_layout bytes, per the header at hdr; the header alone when the children
@@ -177,11 +178,12 @@ hipError_t launch_round_bounds(const uint32_t *rank, const RoundIn &in, const Ro
 // medium rounds (r <= round_small_max()): decisions, offsets and the header in one workgroup
 uint64_t round_small_max();
 hipError_t launch_round_plan_scan(const RoundIn &in, const RoundSegs &g, uint64_t r, uint64_t n, int sqrt_policy,
-                                  uint64_t b, uint8_t *out, hipStream_t st);
+                                  uint64_t b, uint8_t *out, hipStream_t st, uint64_t thr = 0);
 // tiny rounds (r <= round_tiny_max()): from the searched bound ranks to `out` in one launch
 uint64_t round_tiny_max();
 hipError_t launch_round_small(const uint32_t *rank, const RoundIn &in, const RoundSegs &g, uint64_t r, uint64_t n,
-                              int sqrt_policy, uint64_t b, uint64_t cap, uint32_t kl, uint8_t *out, hipStream_t st);
+                              int sqrt_policy, uint64_t b, uint64_t cap, uint32_t kl, uint8_t *out, hipStream_t st,
+                              uint64_t thr = 0);
 hipError_t launch_combine(const uint64_t *in, uint64_t parts, uint64_t r, uint64_t *out, hipStream_t st);
 
 // ---- Enumerate for many key ranges at once (enumerate_kernels.hip; rh_store_enumerate_segments) ----

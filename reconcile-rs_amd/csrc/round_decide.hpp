@@ -10,7 +10,9 @@
 // (fixed_fan_out.rs:74-80), SqrtFanOut (span as f32).sqrt() (sqrt_fan_out.rs) -- a SPLIT that
 // would not progress turned IDLIST (:263-272), an IDLIST with a non-empty remote side bounced
 // back as one child with the ZERO aggregate, a SPLIT's children cut at every stride-th rank
-// (:288-313).  Plain C++: no HIP, no allocation.
+// (:288-313).  EnumerateBelowThreshold (policy/enumerate_below_threshold.rs:141-153), chosen by a
+// non-zero threshold t, replaces the shared cutoffs: SKIP on equal aggregates, IDLIST when
+// span <= t, else SPLIT with stride ceil(span / b).  Plain C++: no HIP, no allocation.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -28,15 +30,18 @@ struct SegDecision {
 };
 
 // lo / hi: the segment's raw ranks (BoundedRange::parse, rbsr/src/protocol/rank.rs); loc: the
-// local aggregate over them (ZERO when hi < lo); rem: the peer's aggregate; b: the fan-out (>= 2)
+// local aggregate over them (ZERO when hi < lo); rem: the peer's aggregate; b: the fan-out (>= 2);
+// thr: EnumerateBelowThreshold's t (>= 1), or 0 for the two policies of the shared cutoffs
 inline SegDecision decide_segment(uint64_t lo, uint64_t hi, const rh_aggregate &loc, const rh_aggregate &rem,
-                                  int sqrt_policy, uint64_t b) {
+                                  int sqrt_policy, uint64_t b, uint64_t thr = 0) {
     SegDecision d{3, 0, 0, 0};
     if (hi < lo) return d;
     const uint64_t span = loc.size, r = rem.size;
     uint64_t st = 0;
     int k;
     if (span == r && !memcmp(loc.fingerprint, rem.fingerprint, 32)) k = 0;
+    else if (thr && span <= thr) k = 1;
+    else if (thr) k = 2, st = span / b + (span % b != 0);  // span > t >= 1: the stride is >= 1
     else if (r == 0) k = 1;
     else if (span == 0) k = 2, st = 1;
     else if (span == 1 && r == 1) k = 1;

@@ -95,13 +95,15 @@ __device__ __forceinline__ void wave_range_agg(const uint8_t *fps, uint32_t stri
 // (protocol.rs:263-272).  An IDLIST with a non-empty remote side bounces its range back as one
 // child with the ZERO aggregate; a SPLIT's children are cut at every stride-th rank
 // (protocol.rs:288-313).  kind: 0 skip, 1 IDLIST, 2 SPLIT, 3 dropped (inverted, :232-245).
+// thr != 0: EnumerateBelowThreshold (policy/enumerate_below_threshold.rs:141-153) in place of the
+// shared cutoffs -- IDLIST when span <= thr, else SPLIT with stride ceil(span / b).
 struct RoundSeg {
     int kind;
     uint64_t stride, si, ei, children, enums;
 };
 
 __device__ __forceinline__ RoundSeg round_decide(uint64_t l, uint64_t h, const uint64_t *L, const uint64_t *R,
-                                                 uint64_t n, int sqrt_policy, uint64_t b) {
+                                                 uint64_t n, int sqrt_policy, uint64_t b, uint64_t thr = 0) {
     RoundSeg g{3, 0, 0, 0, 0, 0};
     if (h < l) return g;
     g.si = l < n ? l : n;
@@ -110,6 +112,8 @@ __device__ __forceinline__ RoundSeg round_decide(uint64_t l, uint64_t h, const u
     uint64_t st = 0;
     int k;
     if (span == rem && L[0] == R[0] && L[1] == R[1] && L[2] == R[2] && L[3] == R[3]) k = 0;
+    else if (thr && span <= thr) k = 1;
+    else if (thr) k = 2, st = span / b + (span % b != 0);  // span > thr >= 1: the stride is >= 1
     else if (rem == 0) k = 1;
     else if (span == 0) k = 2, st = 1;
     else if (span == 1 && rem == 1) k = 1;

@@ -112,7 +112,7 @@ __global__ __launch_bounds__(ROUND_TINY_THREADS) void k_round_tiny(RoundTiny a) 
     if (w == 0) {
         const bool mine = t < r;
         RoundSeg d{3, 0, 0, 0, 0, 0};
-        if (mine) d = round_decide(lo[t], hi[t], loc + 5 * t, rem + 5 * t, a.n, a.sqrt_policy, a.b);
+        if (mine) d = round_decide(lo[t], hi[t], loc + 5 * t, rem + 5 * t, a.n, a.sqrt_policy, a.b, a.thr);
         unsigned long long cs = d.children, es = d.enums;  // inclusive scans
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {

@@ -3175,7 +3175,8 @@ struct rh_store {
     // the buffers the store already holds (en_rows rows) before the total is known, so a call whose
     // rows fit makes one wait; one that outgrows them learns the total, grows them and emits again.
     static constexpr uint64_t ENUM_MAX_ROWS = 1ull << 22;  // as KEYS_VIEW_MAX: no compaction below it
-    PinnedVec<uint8_t> en_in, en_out;
+    // (en_out is polled while k_enum_tiny writes it: coherent, as pr_out and qt_buf)
+    PinnedVec<uint8_t> en_in, en_out{hipHostMallocCoherent};
     DevBuf<uint8_t> en_d, en_hdr, en_keys;  // bounds in; first ranks, offsets, counts, places; rows
     uint64_t en_rows = 0;                   // rows en_keys and en_out have room for
     uint64_t en_none[2] = {0, 0};           // the answer to no ranges (offsets[0] = 0)
@@ -3208,6 +3209,55 @@ struct rh_store {
             tier.copy_keys(first[j], first[j] + (first[r + j + 1] - first[r + j]), en_out.data() + L.keys + first[r + j] * kl);
         return enumerated(r, true, out), RH_OK;
     }
+    // A handful of ranges in one launch (enum_tiny.hpp k_enum_tiny): the ranges in the kernel's
+    // arguments, the answer written into en_out (mapped) in enum_layout, the host polling the
+    // sequence word stored behind the rows' room -- query_tiny's protocol.  The kernel always
+    // writes first ranks, offsets and the total; the rows only when the total is within
+    // ENUM_TINY_ROWS and max_rows.  *done = false: a larger total (the general path below answers,
+    // one more trip) or no device address for en_out.  A/B: RSOS_HIP_ENUM_FUSED=0.
+    int enum_fused = getenv("RSOS_HIP_ENUM_FUSED") ? atoi(getenv("RSOS_HIP_ENUM_FUSED")) : 1;
+    uint64_t en_seq = 0, en_tiny_calls = 0, en_general_calls = 0;  // rh_store_enumerate_stats
+    int enumerate_tiny(const rh_segments &g, uint64_t max_rows, rh_enumerated *out, bool *over, bool *done) {
+        int rc;
+        const size_t r = g.n;
+        const rh::EnumLayout L = rh::enum_layout(r);
+        *done = false;
+        rh::RoundRun run{};
+        if (nd) {
+            rh::RoundIn unused;
+            if ((rc = view_of(&run, &unused))) return rc;
+        }
+        run.nb = nb;
+        const size_t o_seq = L.keys + (size_t)rh::ENUM_TINY_ROWS * kl;  // behind the rows' room
+        en_out.clear();  // (a larger buffer need not keep the last answer)
+        en_out.resize(o_seq + 64);
+        uint8_t *d = nullptr;
+        const std::string keep = g_err;
+        if (dev_ptr(en_out, &d)) return g_err = keep, RH_OK;
+        rh::EnumTiny q{};
+        const uint8_t *skeys = static_cast<const uint8_t *>(g.start_keys), *ekeys = static_cast<const uint8_t *>(g.end_keys);
+        for (size_t j = 0; j < r; j++) {
+            q.isk[j] = g.start_kinds[j], q.iek[j] = g.end_kinds[j];
+            if (q.isk[j]) memcpy(q.ikeys + 2 * j * kl, skeys + j * kl, kl);
+            if (q.iek[j]) memcpy(q.ikeys + (2 * j + 1) * kl, ekeys + j * kl, kl);
+        }
+        q.bkeys = bkeys[cb].p;
+        q.run = run;
+        q.btab = (!bsmp2.p || nb == 0) ? rh::SearchTable{} : base_table();
+        q.r = r, q.limit = std::min<uint64_t>(max_rows, rh::ENUM_TINY_ROWS);
+        uint64_t *word = reinterpret_cast<uint64_t *>(en_out.data() + o_seq);
+        if (fail_point("enum.stale_seq")) *word = en_seq + 1;
+        q.out = d, q.seq_word = reinterpret_cast<uint64_t *>(d + o_seq), q.seq = ++en_seq;
+        disarm(word);
+        RH_HIP(kops->enum_tiny(q, stream));
+        if ((rc = wait_word(word, q.seq))) return rc;
+        const uint64_t total = reinterpret_cast<const uint64_t *>(en_out.data() + L.offs)[r];
+        if (total > q.limit && total <= max_rows) return RH_OK;  // more than the kernel writes: the general path
+        *over = total > max_rows;
+        *done = true;
+        en_tiny_calls++;
+        return enumerated(r, !*over, out), RH_OK;
+    }
     int enumerate_device(const rh_segments &g, uint64_t max_rows, rh_enumerated *out, bool *over) {
         int rc;
         const size_t r = g.n;
@@ -3217,6 +3267,11 @@ struct rh_store {
             en_out.assign(L.keys + 64, 0);
             return enumerated(r, true, out), RH_OK;
         }
+        if (enum_fused && tiny_kernels_serve() && r <= rh::ROUND_TINY_SEGS) {
+            bool done = false;
+            if ((rc = enumerate_tiny(g, max_rows, out, over, &done)) || done) return rc;
+        }
+        en_general_calls++;
         const uint8_t *skeys = static_cast<const uint8_t *>(g.start_keys), *ekeys = static_cast<const uint8_t *>(g.end_keys);
         const size_t kb = pad8(2 * r * kl), in_bytes = kb + pad8(2 * r);
         const size_t o_cnt = L.keys, o_place = o_cnt + 8 * (r + 1), hdr_bytes = o_place + 32 * r;
@@ -3313,13 +3368,14 @@ struct rh_store {
         double h0 = 0, hv = 0, hs = 0, h1 = 0, h2 = 0, l0 = 0, l1 = 0, c0 = 0;
     } rp;
     int protocol_round(int policy, uint64_t param, const rh_segments &in, rh_segments *ch, rh_segments *en,
-                       rh_round_outcome *oc) {
-        const int rc = round_issue(policy, param, in, ch, en, oc);
+                       rh_round_outcome *oc, uint64_t thr = 0) {
+        const int rc = round_issue(policy, param, in, ch, en, oc, thr);
         if (rc || !rp.on) return rc;
         return round_complete(ch, en, oc);
     }
+    // thr: EnumerateBelowThreshold's t (>= 1), or 0 for the policies of the shared cutoffs
     int round_issue(int policy, uint64_t param, const rh_segments &in, rh_segments *ch, rh_segments *en,
-                    rh_round_outcome *oc) {
+                    rh_round_outcome *oc, uint64_t thr = 0) {
         int rc;
         const size_t r = in.n;
         const double h0 = round_dbg ? now_us() : 0;
@@ -3428,6 +3484,7 @@ struct rh_store {
             t.bsmp = bsmp.p, t.bsmp2 = bsmp2.p, t.btab = (!bsmp2.p || nb == 0) ? rh::SearchTable{} : base_table();
             t.dsmp = view ? dsmp[cd].p : nullptr, t.dsmp2 = view ? dsmp2[cd].p : nullptr;
             t.g = g, t.gplace = place, t.r = r, t.n = n, t.sqrt_policy = sq, t.b = b, t.cap = cap, t.out = out_p;
+            t.thr = thr;
             if (fail_point("round.stale_seq")) reinterpret_cast<uint64_t *>(pr_out.data())[7] = round_seq + 1;
             t.seq = ++round_seq;
             disarm(reinterpret_cast<uint64_t *>(pr_out.data()) + 7);
@@ -3445,7 +3502,8 @@ struct rh_store {
             return RH_OK;
         }
         const double l0 = round_dbg ? now_us() : 0;
-        if ((rc = round_launch(r, b, n, sq, cap, worst, zero_copy, out_p, view, din, run, g, place, hdr, d_skeys, d_rem)))
+        if ((rc = round_launch(r, b, n, sq, cap, worst, zero_copy, out_p, view, din, run, g, place, hdr, d_skeys, d_rem,
+                               thr)))
             return rc;
         rp.tiny = false, rp.cap = cap, rp.r = r, rp.worst = worst, rp.zero_copy = zero_copy, rp.direct = rq_direct;
         rp.view = view, rp.din = din, rp.run = run, rp.g = g, rp.place = place;
@@ -3511,7 +3569,7 @@ struct rh_store {
     int round_launch(size_t r, uint64_t b, uint64_t n, int sq, uint64_t cap, size_t worst, bool zero_copy,
                      uint8_t *out_p, bool view, const rh::RoundIn &din, const rh::RoundRun &run,
                      const rh::RoundSegs &g, uint64_t *place, uint64_t *hdr, const uint8_t *d_skeys,
-                     const uint64_t *d_rem) {
+                     const uint64_t *d_rem, uint64_t thr) {
         int rc;
         uint64_t *nch = g.nch, *choff = g.choff, *nen = g.nen, *enoff = g.enoff;
         const double l0 = round_dbg ? now_us() : 0;
@@ -3541,12 +3599,12 @@ struct rh_store {
         if (r <= rh::round_tiny_max()) {
             if (view)
                 RH_HIP(rh::launch_round_small_view(q_rank.p, q_drank.p, din, run, g, place, r, n, sq, b, cap,
-                                                   (uint32_t)kl, out_p, stream));
-            else RH_HIP(rh::launch_round_small(q_rank.p, din, g, r, n, sq, b, cap, (uint32_t)kl, out_p, stream));
+                                                   (uint32_t)kl, out_p, stream, thr));
+            else RH_HIP(rh::launch_round_small(q_rank.p, din, g, r, n, sq, b, cap, (uint32_t)kl, out_p, stream, thr));
         } else if (r <= rh::round_small_max()) {
             if (view) RH_HIP(rh::launch_round_bounds_view(q_rank.p, q_drank.p, din, run, g, place, r, stream));
             else RH_HIP(rh::launch_round_bounds(q_rank.p, din, g, r, n, stream));
-            RH_HIP(rh::launch_round_plan_scan(din, g, r, n, sq, b, out_p, stream));
+            RH_HIP(rh::launch_round_plan_scan(din, g, r, n, sq, b, out_p, stream, thr));
             RH_HIP(emit(cap, reinterpret_cast<const uint64_t *>(out_p), zero_copy ? out_p : eo));
         } else {
             if (view) RH_HIP(rh::launch_round_bounds_view(q_rank.p, q_drank.p, din, run, g, place, r, stream));
@@ -3554,10 +3612,10 @@ struct rh_store {
             const double lb = round_dbg ? now_us() : 0;
             if (plan3) {  // three launches
                 if ((rc = r_part.ensure(5 * ((r + 255) / 256) + 8))) return rc;
-                RH_HIP(rh::launch_round_plan3(g, d_rem, r, n, sq, b, r_part.p, hdr, stream));
+                RH_HIP(rh::launch_round_plan3(g, d_rem, r, n, sq, b, r_part.p, hdr, stream, thr));
             } else {
                 RH_HIP(hipMemsetAsync(hdr, 0, 64, stream));
-                RH_HIP(rh::launch_round_plan(g, d_rem, r, n, sq, b, hdr, stream));
+                RH_HIP(rh::launch_round_plan(g, d_rem, r, n, sq, b, hdr, stream, thr));
             }
             const double lc = round_dbg ? now_us() : 0;
             if (!plan3) {
@@ -3724,7 +3782,7 @@ static int flush_locked(rh_store *s) {
 }
 
 static int round_entry(rh_store *s, int policy, uint64_t fan_out, const rh_segments *active, rh_segments *children,
-                       rh_segments *enumerations, rh_round_outcome *outcome, bool *pending);
+                       rh_segments *enumerations, rh_round_outcome *outcome, bool *pending, uint64_t thr);
 
 // Under the store's lock: 1 if the host tier answers (refreshing it first if the store changed
 // since; only then is the device touched), 0 if the tier is off, < 0 on error
@@ -3977,15 +4035,23 @@ int rh_store_split_segments(rh_store *s, size_t m, const uint64_t *select_ranks,
 
 int rh_store_protocol_round(rh_store *s, int policy, uint64_t fan_out, const rh_segments *active,
                             rh_segments *children, rh_segments *enumerations, rh_round_outcome *outcome) {
-    return round_entry(s, policy, fan_out, active, children, enumerations, outcome, nullptr);
+    return round_entry(s, policy, fan_out, active, children, enumerations, outcome, nullptr, 0);
+}
+
+int rh_store_protocol_round_threshold(rh_store *s, uint64_t threshold, uint64_t fan_out, const rh_segments *active,
+                                      rh_segments *children, rh_segments *enumerations, rh_round_outcome *outcome) {
+    // EnumerateBelowThreshold::new: a threshold of 0 is raised to 1
+    return round_entry(s, RH_POLICY_FIXED_FAN_OUT, fan_out, active, children, enumerations, outcome, nullptr,
+                       threshold ? threshold : 1);
 }
 
 }  // extern "C"
 
 // rh_store_protocol_round; with `pending` non-NULL a device round is only issued: *pending = true,
-// the store stays locked, and rh::store_round_complete finishes it (on the same thread)
+// the store stays locked, and rh::store_round_complete finishes it (on the same thread).
+// thr != 0: EnumerateBelowThreshold(thr, fan_out) in place of `policy`
 static int round_entry(rh_store *s, int policy, uint64_t fan_out, const rh_segments *active, rh_segments *children,
-                       rh_segments *enumerations, rh_round_outcome *outcome, bool *pending) {
+                       rh_segments *enumerations, rh_round_outcome *outcome, bool *pending, uint64_t thr) {
     if (pending) *pending = false;
     if (!s || !active || !children || !enumerations) return fail(RH_ERR_ARG, "NULL");
     if (policy != RH_POLICY_FIXED_FAN_OUT && policy != RH_POLICY_SQRT_FAN_OUT) return fail(RH_ERR_ARG, "unknown policy");
@@ -4009,7 +4075,7 @@ static int round_entry(rh_store *s, int policy, uint64_t fan_out, const rh_segme
             if (t < 0) return t;
             if (t) {
                 uint64_t h[5];
-                s->tier.round(policy == RH_POLICY_SQRT_FAN_OUT, fan_out < 2 ? 2 : fan_out, *active, s->tier_out, h);
+                s->tier.round(policy == RH_POLICY_SQRT_FAN_OUT, fan_out < 2 ? 2 : fan_out, *active, s->tier_out, h, thr);
                 const uint64_t nc = h[3], ne = h[1];
                 const rh::RoundLayout L = rh::round_layout(nc, ne, s->kl);
                 uint8_t *o = s->tier_out.data();
@@ -4032,7 +4098,7 @@ static int round_entry(rh_store *s, int policy, uint64_t fan_out, const rh_segme
         int rc = s->flush();
         if (rc) return rc;
         try {
-            rc = s->round_issue(policy, fan_out, *active, children, enumerations, outcome);
+            rc = s->round_issue(policy, fan_out, *active, children, enumerations, outcome, thr);
         } catch (const std::bad_alloc &) {
             s->rp.on = false;
             *children = rh_segments{};
@@ -4046,7 +4112,7 @@ static int round_entry(rh_store *s, int policy, uint64_t fan_out, const rh_segme
     }
     RH_LOCK(s);
     try {  // no exception crosses the C ABI
-        return s->protocol_round(policy, fan_out, *active, children, enumerations, outcome);
+        return s->protocol_round(policy, fan_out, *active, children, enumerations, outcome, thr);
     } catch (const std::bad_alloc &) {
         *children = rh_segments{};
         *enumerations = rh_segments{};
@@ -4056,8 +4122,8 @@ static int round_entry(rh_store *s, int policy, uint64_t fan_out, const rh_segme
 
 namespace rh {
 int store_round_issue(rh_store *s, int policy, uint64_t fan_out, const rh_segments *active, rh_segments *children,
-                      rh_segments *enumerations, rh_round_outcome *outcome, bool *pending) {
-    return round_entry(s, policy, fan_out, active, children, enumerations, outcome, pending);
+                      rh_segments *enumerations, rh_round_outcome *outcome, bool *pending, uint64_t threshold) {
+    return round_entry(s, policy, fan_out, active, children, enumerations, outcome, pending, threshold);
 }
 int store_round_complete(rh_store *s, rh_segments *children, rh_segments *enumerations, rh_round_outcome *outcome) {
     std::unique_lock<std::mutex> g(s->mu, std::adopt_lock);  // taken by store_round_issue
@@ -4175,6 +4241,14 @@ int rh_store_batch_stats(rh_store *s, uint64_t *small_batches, uint64_t *large_b
     if (rc) return rc;
     if (small_batches) *small_batches = s->small_batches;
     if (large_batches) *large_batches = s->large_batches;
+    return RH_OK;
+}
+
+int rh_store_enumerate_stats(rh_store *s, uint64_t *one_launch, uint64_t *general) {
+    if (!s) return fail(RH_ERR_ARG, "store is NULL");
+    std::lock_guard<std::mutex> g(s->mu);
+    if (one_launch) *one_launch = s->en_tiny_calls;
+    if (general) *general = s->en_general_calls;
     return RH_OK;
 }
 

@@ -1111,8 +1111,9 @@ struct rh_sstore {
     }
     // copying a round's pieces takes the shard threads past this many bytes
     static constexpr size_t PARALLEL_COPY_BYTES = 1 << 20;
+    // thr != 0: EnumerateBelowThreshold(thr, fan_out), in the shards' rounds and the straddling segments
     int protocol_round(int policy, uint64_t fan_out, const rh_segments &in, rh_segments *ch, rh_segments *en,
-                       rh_round_outcome *oc) {
+                       rh_round_outcome *oc, uint64_t thr = 0) {
         const double t0 = dbg() ? now_us() : 0;
         std::vector<double> shard_us(dbg() ? G : 0, 0.0), verify_us(dbg() ? G : 0, 0.0);
         std::vector<Run> runs;
@@ -1141,7 +1142,7 @@ struct rh_sstore {
             // the straddling segments first: their shard calls come before the shards' own rounds,
             // whose outputs then stay in place until the round is assembled
             int rc;
-            if (!cross.empty() && (rc = cross_round(policy, fan_out, in, runs, cross, outs))) return rc;
+            if (!cross.empty() && (rc = cross_round(policy, fan_out, in, runs, cross, outs, thr))) return rc;
             t2 = dbg() ? now_us() : 0;
             std::atomic<bool> unsorted{false};
             auto sub_of = [&](size_t k) {
@@ -1194,7 +1195,7 @@ struct rh_sstore {
                         rh_segments c{}, e{};
                         rh_round_outcome o{};
                         bool pending = false;
-                        const int q = rh::store_round_issue(shards[s], policy, fan_out, &sub, &c, &e, &o, &pending);
+                        const int q = rh::store_round_issue(shards[s], policy, fan_out, &sub, &c, &e, &o, &pending, thr);
                         keep(q);
                         if (!q && pending) pend.emplace_back(s, k);
                         else if (!q) outs[k].borrow(c, e, o);
@@ -1204,7 +1205,8 @@ struct rh_sstore {
                         const rh_segments sub = sub_of(k);
                         rh_segments c{}, e{};
                         rh_round_outcome o{};
-                        const int q = rh_store_protocol_round(shards[s], policy, fan_out, &sub, &c, &e, &o);
+                        const int q = thr ? rh_store_protocol_round_threshold(shards[s], thr, fan_out, &sub, &c, &e, &o)
+                                          : rh_store_protocol_round(shards[s], policy, fan_out, &sub, &c, &e, &o);
                         keep(q);
                         if (q) break;
                         outs[k].take(c, e, o, kl);
@@ -1289,7 +1291,7 @@ struct rh_sstore {
     // the host (decide_segment), their SPLIT cuts selected and their children summed over the
     // shards holding them -- one call per shard for each of the two steps.
     int cross_round(int policy, uint64_t fan_out, const rh_segments &in, const std::vector<Run> &runs,
-                    const std::vector<size_t> &J, std::vector<Out> &outs) {
+                    const std::vector<size_t> &J, std::vector<Out> &outs, uint64_t thr = 0) {
         const uint8_t *sk = in.start_kinds, *ek = in.end_kinds;
         const uint8_t *skeys = static_cast<const uint8_t *>(in.start_keys);
         const uint8_t *ekeys = static_cast<const uint8_t *>(in.end_keys);
@@ -1306,7 +1308,7 @@ struct rh_sstore {
         std::vector<uint64_t> sel, clo, chi;
         std::vector<size_t> first_sel(nj), first_child(nj);
         for (size_t t = 0; t < nj; t++) {
-            d[t] = rh::decide_segment(lo[t], hi[t], loc[t], in.aggregates[J[t]], sq, b);
+            d[t] = rh::decide_segment(lo[t], hi[t], loc[t], in.aggregates[J[t]], sq, b, thr);
             first_sel[t] = sel.size(), first_child[t] = clo.size();
             if (d[t].kind != 2 || d[t].children < 2) continue;
             const uint64_t ncuts = d[t].children - 1;
@@ -2098,8 +2100,9 @@ int rh_sstore_split_segments(rh_sstore *s, size_t m, const uint64_t *select_rank
     }
 }
 
-int rh_sstore_protocol_round(rh_sstore *s, int policy, uint64_t fan_out, const rh_segments *active,
-                             rh_segments *children, rh_segments *enumerations, rh_round_outcome *outcome) {
+// rh_sstore_protocol_round and, with thr != 0, rh_sstore_protocol_round_threshold
+static int sstore_round(rh_sstore *s, int policy, uint64_t fan_out, const rh_segments *active, rh_segments *children,
+                        rh_segments *enumerations, rh_round_outcome *outcome, uint64_t thr) {
     if (!s || !active || !children || !enumerations) return fail(RH_ERR_ARG, "NULL");
     if (policy != RH_POLICY_FIXED_FAN_OUT && policy != RH_POLICY_SQRT_FAN_OUT) return fail(RH_ERR_ARG, "unknown policy");
     const size_t r = active->n;
@@ -2119,7 +2122,7 @@ int rh_sstore_protocol_round(rh_sstore *s, int policy, uint64_t fan_out, const r
     int rc = lock_sizes(s, g);
     if (rc) return rc;
     try {
-        rc = s->protocol_round(policy, fan_out, *active, children, enumerations, outcome);
+        rc = s->protocol_round(policy, fan_out, *active, children, enumerations, outcome, thr);
     } catch (const std::bad_alloc &) {
         rc = fail(RH_ERR_OOM, "protocol round: host allocation failed");
     } catch (...) {  // nothing crosses the C ABI
@@ -2131,6 +2134,18 @@ int rh_sstore_protocol_round(rh_sstore *s, int policy, uint64_t fan_out, const r
         if (outcome) *outcome = rh_round_outcome{};
     }
     return rc;
+}
+
+int rh_sstore_protocol_round(rh_sstore *s, int policy, uint64_t fan_out, const rh_segments *active,
+                             rh_segments *children, rh_segments *enumerations, rh_round_outcome *outcome) {
+    return sstore_round(s, policy, fan_out, active, children, enumerations, outcome, 0);
+}
+
+int rh_sstore_protocol_round_threshold(rh_sstore *s, uint64_t threshold, uint64_t fan_out, const rh_segments *active,
+                                       rh_segments *children, rh_segments *enumerations, rh_round_outcome *outcome) {
+    // EnumerateBelowThreshold::new: a threshold of 0 is raised to 1
+    return sstore_round(s, RH_POLICY_FIXED_FAN_OUT, fan_out, active, children, enumerations, outcome,
+                        threshold ? threshold : 1);
 }
 
 int rh_sstore_enumerate_segments(rh_sstore *s, const rh_segments *ranges, uint64_t max_rows, rh_enumerated *out) {

@@ -31,6 +31,7 @@
 #include "search_device.hpp"
 #include "fp_device.hpp"
 #include "round_tiny.hpp"
+#include "enum_tiny.hpp"
 
 namespace rh {
 
@@ -1675,6 +1676,16 @@ struct KeyOps final : StoreKeyOps {
         if constexpr (KL <= (int)ROUND_TINY_KL) {
             if (a.r == 0 || a.r > ROUND_TINY) return hipErrorInvalidValue;
             hipLaunchKernelGGL((k_round_tiny<KK, KL>), dim3(1), dim3(ROUND_TINY_THREADS), 0, st, a);
+            return hipGetLastError();
+        } else {
+            return hipErrorInvalidValue;
+        }
+    }
+
+    hipError_t enum_tiny(const EnumTiny &a, hipStream_t st) override {
+        if constexpr (KL <= (int)ROUND_TINY_KL) {
+            if (a.r == 0 || a.r > ROUND_TINY_SEGS || a.limit > ENUM_TINY_ROWS) return hipErrorInvalidValue;
+            hipLaunchKernelGGL((k_enum_tiny<KK, KL>), dim3(1), dim3(ENUM_TINY_THREADS), 0, st, a);
             return hipGetLastError();
         } else {
             return hipErrorInvalidValue;

@@ -139,6 +139,7 @@ struct RoundTiny {
     uint8_t *out;                  // round_layout (mapped page-locked)
     uint64_t seq;                  // stored to out word 7 last
     uint64_t *dbg;                 // nullable: per-phase real-time clocks (RSOS_HIP_ROUND_DBG)
+    uint64_t thr;                  // EnumerateBelowThreshold's t, or 0: the shared cutoffs (round_decide)
 };
 
 // The small questions in one launch (round_tiny.hpp k_query_tiny), over the base run and any delta
@@ -159,6 +160,24 @@ struct QueryTiny {
     SearchTable btab;
     const uint64_t *dsmp, *dsmp2;
     uint8_t *out;          // mode 0: m u64; 1: m keys; 2: one rh_aggregate
+    uint64_t *seq_word;
+    uint64_t seq;
+};
+
+// Enumerate for a handful of ranges in one launch (enum_tiny.hpp k_enum_tiny): r <= ROUND_TINY_SEGS
+// ranges whose rows number at most ENUM_TINY_ROWS in all (16 ranges of the paper's t = 32), over the
+// base run and any delta run.  The ranges in the kernel's arguments, the answer in mapped
+// page-locked memory in enum_layout(r), a sequence word stored last.
+constexpr uint32_t ENUM_TINY_ROWS = 512;
+struct EnumTiny {
+    uint8_t ikeys[2 * ROUND_TINY_SEGS * ROUND_TINY_KL];  // row 2 j range j's start key, 2 j + 1 its end key
+    uint8_t isk[ROUND_TINY_SEGS], iek[ROUND_TINY_SEGS];  // bound kinds: 0 Unbounded, 1 a key
+    const uint8_t *bkeys;  // the base run's keys
+    RoundRun run;          // run.n == 0: no delta run (run.nb = the base rows either way)
+    SearchTable btab;
+    uint64_t r;
+    uint64_t limit;        // the rows are written only when the total is at most this (<= ENUM_TINY_ROWS)
+    uint8_t *out;          // enum_layout(r): first ranks, offsets (always written), rows
     uint64_t *seq_word;
     uint64_t seq;
 };
@@ -214,6 +233,8 @@ struct StoreKeyOps {
     virtual hipError_t round_tiny(const RoundTiny &a, hipStream_t st) = 0;
     // ranks, selects or a key-range aggregate (QueryTiny) in one launch of one workgroup
     virtual hipError_t query_tiny(const QueryTiny &a, hipStream_t st) = 0;
+    // the keys of a.r <= ROUND_TINY_SEGS ranges (EnumTiny) in one launch of one workgroup
+    virtual hipError_t enum_tiny(const EnumTiny &a, hipStream_t st) = 0;
 };
 
 // Σ count deltas of delta rows [0, i] = sblk[i / 65536] (exclusive super-block prefix)

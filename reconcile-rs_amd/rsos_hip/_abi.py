@@ -105,7 +105,11 @@ SIGNATURES = [
     ("rh_store_split_segments", C.c_int, [P, SZ, U64P, VP, SZ, U64P, U64P, P]),
     ("rh_store_protocol_round", C.c_int, [P, C.c_int, C.c_uint64, C.POINTER(Segments), C.POINTER(Segments),
                                           C.POINTER(Segments), C.POINTER(RoundOutcome)]),
+    ("rh_store_protocol_round_threshold", C.c_int, [P, C.c_uint64, C.c_uint64, C.POINTER(Segments),
+                                                    C.POINTER(Segments), C.POINTER(Segments),
+                                                    C.POINTER(RoundOutcome)]),
     ("rh_store_enumerate_segments", C.c_int, [P, C.POINTER(Segments), C.c_uint64, C.POINTER(Enumerated)]),
+    ("rh_store_enumerate_stats", C.c_int, [P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("rh_store_apply", C.c_int, [P, C.POINTER(Columns), U8P, SZ, C.POINTER(C.c_uint64),
                                  C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("rh_store_apply_device", C.c_int, [P, C.POINTER(Columns), U8P, SZ, C.POINTER(C.c_uint64),
@@ -174,6 +178,9 @@ SIGNATURES = [
     ("rh_sstore_split_segments", C.c_int, [P, SZ, U64P, VP, SZ, U64P, U64P, P]),
     ("rh_sstore_protocol_round", C.c_int, [P, C.c_int, C.c_uint64, C.POINTER(Segments), C.POINTER(Segments),
                                            C.POINTER(Segments), C.POINTER(RoundOutcome)]),
+    ("rh_sstore_protocol_round_threshold", C.c_int, [P, C.c_uint64, C.c_uint64, C.POINTER(Segments),
+                                                     C.POINTER(Segments), C.POINTER(Segments),
+                                                     C.POINTER(RoundOutcome)]),
     ("rh_sstore_enumerate_segments", C.c_int, [P, C.POINTER(Segments), C.c_uint64, C.POINTER(Enumerated)]),
     ("rh_sstore_set_host_tier", C.c_int, [P, C.c_int, C.c_uint64]),
     ("rh_sstore_set_tier_policy", C.c_int, [P, C.c_int]),

@@ -9,6 +9,7 @@ Host-side mirror of rbsr/src/protocol.rs (names, argument meaning, outputs):
   Comparison, FixedFanOut, SqrtFanOut, FanOut,
   SplitStride rules                                       rbsr/src/policy/{comparison,cutoffs,
                                                           fixed_fan_out,sqrt_fan_out,params}.rs
+  EnumerateBelowThreshold                                 rbsr/src/policy/enumerate_below_threshold.rs
 
 The reference walks the active segments one by one and asks its RsosView four questions per
 segment and two per SPLIT child, each an O(log n) tree walk.  Against an HBM-resident store each
@@ -21,8 +22,9 @@ question would be a device round trip, so the round is answered in two batched c
      rh_store_split_segments then returns the keys at every SPLIT cut (`select`, :305) and the
      aggregate of every child that is not the parent itself (:297-307).
 
-For FixedFanOut and SqrtFanOut, which decide on the span alone, the whole round runs inside
-the library instead (rh_store_protocol_round: the same two device steps with the decision loop
+For FixedFanOut, SqrtFanOut and EnumerateBelowThreshold, which decide on the span alone, the whole
+round runs inside the library instead (rh_store_protocol_round, rh_store_protocol_round_threshold
+for the third: the same two device steps with the decision loop
 in C++ between them), on segments in the wire codec's SoA form (`Segments`); a reconciliation
 that never leaves that form (protocol_round_segments) touches no per-segment Python object.
 
@@ -122,6 +124,25 @@ class SqrtFanOut:
         if d is not None:
             return d
         return Split(int(np.sqrt(np.float32(c.span()))))
+
+
+class EnumerateBelowThreshold:
+    """Algorithm 1 as written (enumerate_below_threshold.rs:141-153): SKIP on equal aggregates, IDLIST
+    when the local span is at most `threshold`, else SPLIT with stride ceil(span / fan_out).
+    `threshold` 0 is raised to 1 (:117-122), `fan_out` < 2 to 2 (FanOut::new); the defaults are
+    EnumerateBelowThreshold::PAPER (t = 32, b = 16).  Since t >= 1 it subsumes the shared cutoffs,
+    except that a span of 0 or 1 against a larger remote side is an IDLIST, not a stride-1 split."""
+
+    def __init__(self, threshold: int = 32, fan_out: int = 16):
+        self.threshold = 1 if threshold == 0 else threshold
+        self.fan_out = 2 if fan_out < 2 else fan_out  # FanOut::new, as fan_out() above
+
+    def decide(self, c: Comparison):
+        if c.agrees():
+            return SKIP
+        if c.span() <= self.threshold:
+            return ENUMERATE
+        return Split(-(-c.span() // self.fan_out))
 
 
 DEFAULT_POLICY = FixedFanOut(16)
@@ -263,20 +284,23 @@ class RawSegments:
 
 def protocol_round_segments(store, policy, active,
                             copy: bool = True, raw: bool = False) -> Tuple[Segments, Segments, RoundOutcome]:
-    """One round of FixedFanOut / SqrtFanOut inside the library: (children, enumerations, outcome).
+    """One round of FixedFanOut / SqrtFanOut / EnumerateBelowThreshold inside the library: (children,
+    enumerations, outcome).
     copy=False returns views of the store's own output arrays, valid until the store's next call
     (enough to hand the children to the peer store's round); raw=True returns them as RawSegments
     (no views at all).  `active`: Segments or RawSegments."""
     if isinstance(policy, FixedFanOut):
-        kind, b = A.POLICY_FIXED_FAN_OUT, policy.fan_out
+        name, kind, b = "protocol_round", A.POLICY_FIXED_FAN_OUT, policy.fan_out
     elif isinstance(policy, SqrtFanOut):
-        kind, b = A.POLICY_SQRT_FAN_OUT, 0
+        name, kind, b = "protocol_round", A.POLICY_SQRT_FAN_OUT, 0
+    elif isinstance(policy, EnumerateBelowThreshold):
+        name, kind, b = "protocol_round_threshold", policy.threshold, policy.fan_out  # kind: the threshold
     else:
-        raise TypeError("protocol_round_segments runs FixedFanOut / SqrtFanOut; use protocol_round_with_policy")
+        raise TypeError("protocol_round_segments runs FixedFanOut / SqrtFanOut / EnumerateBelowThreshold; "
+                        "use protocol_round_with_policy")
     kl = store.schema.key_row
     a, cc, ec, oc = active.c(), A.Segments(), A.Segments(), A.RoundOutcome()
-    A.check(store._f("protocol_round")(store._h, kind, b, C.byref(a), C.byref(cc), C.byref(ec), C.byref(oc)),
-            store._P + "protocol_round")
+    A.check(store._f(name)(store._h, kind, b, C.byref(a), C.byref(cc), C.byref(ec), C.byref(oc)), store._P + name)
     if raw:
         return (RawSegments(cc), RawSegments(ec),
                 RoundOutcome(int(oc.skipped), int(oc.enumerated), int(oc.split), int(oc.children),
@@ -325,9 +349,9 @@ def protocol_round_with_policy(local, policy, active: Sequence[RangeAggregate],
                                child_ranges: List[RangeAggregate],
                                enumeration_ranges: List[EnumerationRange], native: Optional[bool] = None) -> RoundOutcome:
     """native: None = the library's one-call round when the policy allows it (FixedFanOut,
-    SqrtFanOut) and `local` is a GpuFingerprintStore; False = the two-call path for any policy."""
+    SqrtFanOut, EnumerateBelowThreshold) and `local` is a GpuFingerprintStore; False = the two-call path for any policy."""
     if native is None:
-        native = isinstance(policy, (FixedFanOut, SqrtFanOut)) and hasattr(local, "_h")
+        native = isinstance(policy, (FixedFanOut, SqrtFanOut, EnumerateBelowThreshold)) and hasattr(local, "_h")
     if native:
         ch, en, outcome = protocol_round_segments(local, policy, Segments.from_items(local.schema, active))
         child_ranges.extend(ch.items(local.schema))

@@ -128,6 +128,14 @@ class ShardedStore(GpuFingerprintStore):
                 out[k] += v
         return out
 
+    def enumerate_stats(self) -> Dict[str, int]:
+        """The shards' device enumerate calls, summed (rh_store_enumerate_stats of each shard)."""
+        out = {"one_launch": 0, "general": 0}
+        for s in self.shards:
+            for k, v in s.enumerate_stats().items():
+                out[k] += v
+        return out
+
     def tier_sync(self) -> None:
         for s in self.shards:
             s.tier_sync()

@@ -235,6 +235,13 @@ class GpuFingerprintStore:
         A.check(self._f("batch_stats")(self._h, C.byref(a), C.byref(b)), "rh_store_batch_stats")
         return {"small": int(a.value), "large": int(b.value)}
 
+    def enumerate_stats(self) -> Dict[str, int]:
+        """Device enumerate calls answered by the one-launch kernel and by the general path
+        (rh_store_enumerate_stats); host-tier answers and empty stores count as neither."""
+        a, b = C.c_uint64(), C.c_uint64()
+        A.check(A.lib().rh_store_enumerate_stats(self._h, C.byref(a), C.byref(b)), "rh_store_enumerate_stats")
+        return {"one_launch": int(a.value), "general": int(b.value)}
+
     def stage(self, cols: Dict[str, np.ndarray], ops: np.ndarray) -> None:
         """Queue host rows (rh_store_stage): applied as one batch by the next call that reads the
         store; a key staged more than once keeps its last operation."""

@@ -188,8 +188,12 @@ extern "C" {
     pub fn rh_store_protocol_round(store: *mut rh_store, policy: c_int, fan_out: u64, active: *const rh_segments,
                                    children: *mut rh_segments, enumerations: *mut rh_segments,
                                    outcome: *mut rh_round_outcome) -> c_int;
+    pub fn rh_store_protocol_round_threshold(store: *mut rh_store, threshold: u64, fan_out: u64,
+                                             active: *const rh_segments, children: *mut rh_segments,
+                                             enumerations: *mut rh_segments, outcome: *mut rh_round_outcome) -> c_int;
     pub fn rh_store_enumerate_segments(store: *mut rh_store, ranges: *const rh_segments, max_rows: u64,
                                        out: *mut rh_enumerated) -> c_int;
+    pub fn rh_store_enumerate_stats(store: *mut rh_store, one_launch: *mut u64, general: *mut u64) -> c_int;
     pub fn rh_store_apply(store: *mut rh_store, cols: *const rh_columns, ops: *const u8, n: usize,
                           n_new: *mut u64, n_over: *mut u64, n_del: *mut u64) -> c_int;
     pub fn rh_store_apply_device(store: *mut rh_store, dev_cols: *const rh_columns, dev_ops: *const u8, n: usize,
@@ -286,6 +290,9 @@ extern "C" {
     pub fn rh_sstore_protocol_round(store: *mut rh_sstore, policy: c_int, fan_out: u64, active: *const rh_segments,
                                     children: *mut rh_segments, enumerations: *mut rh_segments,
                                     outcome: *mut rh_round_outcome) -> c_int;
+    pub fn rh_sstore_protocol_round_threshold(store: *mut rh_sstore, threshold: u64, fan_out: u64,
+                                              active: *const rh_segments, children: *mut rh_segments,
+                                              enumerations: *mut rh_segments, outcome: *mut rh_round_outcome) -> c_int;
     pub fn rh_sstore_enumerate_segments(store: *mut rh_sstore, ranges: *const rh_segments, max_rows: u64,
                                         out: *mut rh_enumerated) -> c_int;
     pub fn rh_sstore_set_host_tier(store: *mut rh_sstore, enable: c_int, round_max: u64) -> c_int;

@@ -344,7 +344,8 @@ pub struct RoundCounts {
 
 impl<K: GpuKey, V: GpuRecord> HipFingerprintMap<K, V> {
     /// One `rbsr` protocol round (`protocol_round_with_policy`, rbsr/src/protocol.rs:212-317) answered
-    /// by the library in one call (`rh_store_protocol_round`): from the host tier for rounds of up
+    /// by the library in one call (`rh_store_protocol_round`, or `rh_store_protocol_round_threshold`
+    /// for `RoundPolicy::EnumerateBelowThreshold`): from the host tier for rounds of up
     /// to 128 segments, else in one device round trip.  Outputs are appended in the reference's
     /// order; any other `RefinementPolicy` goes through `rbsr::protocol_round_with_policy` on the
     /// `Rsos<K>` surface.
@@ -359,7 +360,12 @@ impl<K: GpuKey, V: GpuRecord> HipFingerprintMap<K, V> {
         let store = self.store.0;
         // SAFETY: the handle is live for &self; run_round passes valid segment buffers.
         round::run_round(
-            |p, b, a, c, e, o| unsafe { ffi::rh_store_protocol_round(store, p, b, a, c, e, o) },
+            |w, a, c, e, o| unsafe {
+                match w {
+                    round::RoundCall::Policy(p, b) => ffi::rh_store_protocol_round(store, p, b, a, c, e, o),
+                    round::RoundCall::Threshold(t, b) => ffi::rh_store_protocol_round_threshold(store, t, b, a, c, e, o),
+                }
+            },
             policy,
             active,
             child_ranges,

@@ -1,6 +1,8 @@
 //! One `rbsr` protocol round answered inside the library (`rh_store_protocol_round` /
 //! `rh_sstore_protocol_round`, include/rsos_hip.h): `protocol_round_with_policy`
-//! (rbsr/src/protocol.rs:212-317) for the policies that decide on the span alone.
+//! (rbsr/src/protocol.rs:212-317) for the policies that decide on the span alone, and
+//! `rh_store_protocol_round_threshold` / `rh_sstore_protocol_round_threshold` for
+//! `EnumerateBelowThreshold` (rbsr/src/policy/enumerate_below_threshold.rs).
 //!
 //! The round's logic -- the shared cutoffs (policy/cutoffs.rs:21-38), the policy's stride
 //! (fixed_fan_out.rs:74-80, sqrt_fan_out.rs), the cut rule (protocol/rank.rs:75-78), the
@@ -17,19 +19,35 @@ use rsos::{Aggregate, Fingerprint};
 use crate::{check, ffi, GpuKey, RoundCounts};
 
 /// The shipped policies the library decides on the device or its host tier: `FixedFanOut(b)`
-/// (`b < 2` is raised to 2, `FanOut::new`; 16 = `FanOut::NEGENTROPY`, `protocol_round`'s default)
-/// and `SqrtFanOut`.
+/// (`b < 2` is raised to 2, `FanOut::new`; 16 = `FanOut::NEGENTROPY`, `protocol_round`'s default),
+/// `SqrtFanOut`, and `EnumerateBelowThreshold { threshold, fan_out }` (Algorithm 1 as written:
+/// IDLIST when the local span is at most `threshold`, `SPLITBYRANK(fan_out)` otherwise; a
+/// `threshold` of 0 is raised to 1, `EnumerateBelowThreshold::new`).
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
 pub enum RoundPolicy {
     FixedFanOut(usize),
     SqrtFanOut,
+    EnumerateBelowThreshold { threshold: usize, fan_out: usize },
 }
 
-/// `call(policy, fan_out, active, children, enumerations, outcome)` is one of the two entry
-/// points on the caller's store; the outputs it fills point into the store's own buffers, read
+impl RoundPolicy {
+    /// `EnumerateBelowThreshold::PAPER` (enumerate_below_threshold.rs:110-113): `t = 32`, `b = 16`.
+    pub const PAPER: RoundPolicy = RoundPolicy::EnumerateBelowThreshold { threshold: 32, fan_out: 16 };
+}
+
+/// Which entry point a round takes, with its two leading arguments: `Policy(policy, fan_out)` is
+/// `rh_[s]store_protocol_round`, `Threshold(threshold, fan_out)` `rh_[s]store_protocol_round_threshold`.
+#[derive(Clone, Copy, Debug)]
+pub(crate) enum RoundCall {
+    Policy(c_int, u64),
+    Threshold(u64, u64),
+}
+
+/// `call(which, active, children, enumerations, outcome)` makes the entry point `which` names
+/// on the caller's store; the outputs it fills point into the store's own buffers, read
 /// here before anything else can call the store (the caller holds its round lock).
 pub(crate) fn run_round<K: GpuKey>(
-    call: impl FnOnce(c_int, u64, *const ffi::rh_segments, *mut ffi::rh_segments, *mut ffi::rh_segments,
+    call: impl FnOnce(RoundCall, *const ffi::rh_segments, *mut ffi::rh_segments, *mut ffi::rh_segments,
                       *mut ffi::rh_round_outcome) -> c_int,
     policy: RoundPolicy,
     active: Vec<rbsr::RangeAggregate<K>>,
@@ -72,9 +90,10 @@ pub(crate) fn run_round<K: GpuKey>(
         n,
         cap: n,
     };
-    let (kind, b) = match policy {
-        RoundPolicy::FixedFanOut(b) => (ffi::RH_POLICY_FIXED_FAN_OUT, b as u64),
-        RoundPolicy::SqrtFanOut => (ffi::RH_POLICY_SQRT_FAN_OUT, 0),
+    let which = match policy {
+        RoundPolicy::FixedFanOut(b) => RoundCall::Policy(ffi::RH_POLICY_FIXED_FAN_OUT, b as u64),
+        RoundPolicy::SqrtFanOut => RoundCall::Policy(ffi::RH_POLICY_SQRT_FAN_OUT, 0),
+        RoundPolicy::EnumerateBelowThreshold { threshold, fan_out } => RoundCall::Threshold(threshold as u64, fan_out as u64),
     };
     let empty = ffi::rh_segments {
         start_kinds: std::ptr::null_mut(),
@@ -86,7 +105,7 @@ pub(crate) fn run_round<K: GpuKey>(
         cap: 0,
     };
     let (mut ch, mut en, mut oc) = (empty, empty, ffi::rh_round_outcome::default());
-    check(call(kind, b, &input, &mut ch, &mut en, &mut oc), "protocol_round");
+    check(call(which, &input, &mut ch, &mut en, &mut oc), "protocol_round");
     // SAFETY: the library filled ch / en with arrays of ch.n / en.n items (keys kl bytes each),
     // valid until the store's next call, which the caller's round lock excludes.
     unsafe {

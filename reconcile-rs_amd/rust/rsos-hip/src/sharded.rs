@@ -21,7 +21,7 @@ use std::os::raw::{c_int, c_void};
 
 use rsos::{Aggregate, Fingerprint, Rsos};
 
-use crate::round::{run_enumerate, run_round, RoundPolicy};
+use crate::round::{run_enumerate, run_round, RoundCall, RoundPolicy};
 use crate::{check, ffi, schema, sorted, Batch, GpuKey, GpuRecord, RoundCounts};
 
 /// The library's sharded store, owned (its one `Drop`; see `StoreHandle`).
@@ -220,7 +220,12 @@ impl<K: GpuKey, V: GpuRecord> HipShardedMap<K, V> {
         let store = self.store.0;
         // SAFETY: the handle is live for &self; run_round passes valid segment buffers.
         run_round(
-            |p, b, a, c, e, o| unsafe { ffi::rh_sstore_protocol_round(store, p, b, a, c, e, o) },
+            |w, a, c, e, o| unsafe {
+                match w {
+                    RoundCall::Policy(p, b) => ffi::rh_sstore_protocol_round(store, p, b, a, c, e, o),
+                    RoundCall::Threshold(t, b) => ffi::rh_sstore_protocol_round_threshold(store, t, b, a, c, e, o),
+                }
+            },
             policy,
             active,
             child_ranges,
